@@ -16,14 +16,91 @@ as the bucket arena for RCCL all-reduce (dcr_amd/parallel/ddp.py).
 
 Flatten AFTER moving the model to its device; ``p.data`` is replaced by
 buffer views.
+
+``state_bits=8`` (``--use_8bit_adam``) holds both moments as block-scaled
+FP8 instead of fp32 — 2 B + 8 B/256 of state per parameter instead of 8 B.
+The format (normative; checkpoints and ops/hip/adamw8.hip depend on it):
+
+* a quantisation block is 256 consecutive elements of the flat arena
+  (blocks ignore parameter boundaries), ``nblocks = ceil(numel / 256)``;
+* per moment: codes ``uint8[nblocks*256]`` + ``absmax float32[nblocks]``;
+  padding bytes past ``numel`` are 0 and stay 0;
+* codes are OCP FP8 e4m3fn (``torch.float8_e4m3fn``: max 448, no inf):
+  ``code = e4m3fn_rne(clamp(x * (448/absmax), -448, 448))``, ``absmax`` the
+  block's ``max|x|``; dequantise as ``float(code) * (absmax/448)``; a block
+  whose ``448/absmax`` is not finite (``absmax == 0``, or below ~1.3e-36
+  where the scale overflows) is a zero block: codes 0, absmax 0;
+* the first moment is stored as is, the second as ``r = sqrt(v)`` (halves
+  the dynamic range a block spans; sign bit always 0).
+
+One step dequantises, updates in fp32 with the UNquantised ``m'``/``v'``,
+and requantises; rounding is to nearest even, deterministic.
 """
 from __future__ import annotations
 
-from typing import Iterable, List
+from typing import Iterable, List, Tuple
 
 import torch
 
 from . import use_hip, require_hip, count_dispatch
+
+QBLOCK = 256
+FP8_MAX = 448.0
+STATE_FORMAT = {"state_bits": 8, "qblock": QBLOCK, "codec": "e4m3fn_absmax",
+                "second_moment": "sqrt"}
+
+
+def _nblocks(numel: int) -> int:
+    return (numel + QBLOCK - 1) // QBLOCK
+
+
+def _sqrt_rn(x: torch.Tensor) -> torch.Tensor:
+    """Correctly rounded fp32 square root (through fp64), as the kernel's
+    sqrtf is; torch's vectorised CPU sqrt is off by one ulp now and then."""
+    return x.double().sqrt().float()
+
+
+@torch.no_grad()
+def quantize_blockwise(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Flat tensor -> (codes uint8[nblocks*256], absmax float32[nblocks]) in
+    the format of the module docstring. The FP8 cast itself runs on the CPU
+    (``.to(torch.float8_e4m3fn)``); results come back on ``x``'s device."""
+    dev = x.device
+    x = x.detach().reshape(-1).float()
+    nb = _nblocks(x.numel())
+    xp = torch.zeros(nb * QBLOCK, dtype=torch.float32, device=dev)
+    xp[: x.numel()] = x
+    xp = xp.view(nb, QBLOCK)
+    absmax = xp.abs().amax(dim=1)
+    # a true division: `448 / tensor` is reciprocal-then-multiply in torch,
+    # one rounding too many to agree with the kernel at FP8 rounding ties
+    scale = torch.full_like(absmax, FP8_MAX).div(absmax)
+    # the scale is not finite for absmax == 0 and for absmax below
+    # 448/FLT_MAX (~1.3e-36), where 0 * inf would put NaN codes on the
+    # block's zeros: such a block is stored as a zero block (codes 0 — not
+    # the 0x80 of a negative zero — and absmax 0). A NaN absmax stays NaN.
+    ok = torch.isfinite(scale)
+    scale = torch.where(ok, scale, torch.zeros_like(scale))
+    y = (xp * scale[:, None]).clamp_(-FP8_MAX, FP8_MAX)
+    codes = y.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(dev)
+    codes = torch.where(ok[:, None], codes, torch.zeros_like(codes))
+    absmax = torch.where(ok | absmax.isnan(), absmax, torch.zeros_like(absmax))
+    return codes.reshape(-1).contiguous(), absmax.contiguous()
+
+
+@torch.no_grad()
+def dequantize_blockwise(codes: torch.Tensor, absmax: torch.Tensor,
+                         numel: int) -> torch.Tensor:
+    """Inverse of quantize_blockwise: float32[numel]."""
+    dev = codes.device
+    nb = absmax.numel()
+    if codes.numel() != nb * QBLOCK or _nblocks(numel) != nb:
+        raise ValueError(
+            f"dequantize_blockwise: {codes.numel()} codes / {nb} blocks do "
+            f"not describe {numel} elements")
+    f = codes.detach().cpu().contiguous().view(torch.float8_e4m3fn).float().to(dev)
+    out = f.view(nb, QBLOCK) * (absmax.float() / FP8_MAX)[:, None]
+    return out.reshape(-1)[:numel].contiguous()
 
 
 class FusedAdamW:
@@ -36,7 +113,15 @@ class FusedAdamW:
         weight_decay: float = 1e-2,
         device_state: bool = False,
         max_grad_norm: float = 1.0,
+        state_bits: int = 32,
     ):
+        if state_bits not in (32, 8):
+            raise ValueError(f"FusedAdamW: state_bits must be 32 or 8, got {state_bits}")
+        if state_bits == 8 and device_state:
+            raise ValueError(
+                "FusedAdamW: no device-state (graph-capturable) step exists "
+                "for 8-bit optimizer state; use device_state=False")
+        self.state_bits = state_bits
         self.lr = lr
         self.beta1, self.beta2 = betas
         self.eps = eps
@@ -56,8 +141,17 @@ class FusedAdamW:
         total = sum(p.numel() for p in self.params)
         self.flat_param = torch.empty(total, device=device, dtype=dtype)
         self.flat_grad = torch.zeros(total, device=device, dtype=dtype)
-        self.exp_avg = torch.zeros(total, device=device, dtype=torch.float32)
-        self.exp_avg_sq = torch.zeros(total, device=device, dtype=torch.float32)
+        if state_bits == 8:
+            # block-scaled FP8 moments (module docstring); no fp32 arenas
+            nb = _nblocks(total)
+            self.exp_avg = self.exp_avg_sq = None
+            self.exp_avg_q = torch.zeros(nb * QBLOCK, device=device, dtype=torch.uint8)
+            self.exp_avg_absmax = torch.zeros(nb, device=device, dtype=torch.float32)
+            self.exp_avg_sq_q = torch.zeros(nb * QBLOCK, device=device, dtype=torch.uint8)
+            self.exp_avg_sq_absmax = torch.zeros(nb, device=device, dtype=torch.float32)
+        else:
+            self.exp_avg = torch.zeros(total, device=device, dtype=torch.float32)
+            self.exp_avg_sq = torch.zeros(total, device=device, dtype=torch.float32)
         # pure-bf16 training: bf16 model params/grads + fp32 master copy
         self.master = None
         if dtype == torch.bfloat16:
@@ -181,6 +275,9 @@ class FusedAdamW:
             self.lr = lr
         self.step_count += 1
         t = self.step_count
+        if self.state_bits == 8:
+            self._step8(t)
+            return
         if use_hip(self.flat_param):
             m = require_hip("adamw")
             if m is not None:
@@ -212,6 +309,60 @@ class FusedAdamW:
                 (upd + self.weight_decay * self.flat_param.float()).to(self.flat_param.dtype),
                 alpha=-self.lr,
             )
+
+    def _step8(self, t: int):
+        """One step on block-scaled FP8 state (format: module docstring)."""
+        if use_hip(self.flat_param):
+            m = require_hip("adamw8")
+            if m is not None:
+                count_dispatch('adamw8')
+                if self.master is not None:
+                    m.adamw8_step_bf16(
+                        self.flat_param, self.flat_grad, self.master,
+                        self.exp_avg_q, self.exp_avg_absmax,
+                        self.exp_avg_sq_q, self.exp_avg_sq_absmax, self.lr,
+                        self.beta1, self.beta2, self.eps, self.weight_decay, t)
+                else:
+                    m.adamw8_step(
+                        self.flat_param, self.flat_grad,
+                        self.exp_avg_q, self.exp_avg_absmax,
+                        self.exp_avg_sq_q, self.exp_avg_sq_absmax, self.lr,
+                        self.beta1, self.beta2, self.eps, self.weight_decay, t)
+                return
+        # reference implementation (CPU tests / debug fallback). Every
+        # multiply and add is its own torch op (no `alpha=`/addcmul, which
+        # fuse into FMAs on some CPU paths) and the scalars are formed in
+        # double then rounded once — the kernel does the same, so the two
+        # agree to the last bit (sqrt and divide round correctly on both).
+        n = self.numel
+        inv_bc1 = 1.0 / (1.0 - self.beta1 ** t)
+        inv_bc2 = 1.0 / (1.0 - self.beta2 ** t)
+        g = self.flat_grad.float()
+        m_ = dequantize_blockwise(self.exp_avg_q, self.exp_avg_absmax, n)
+        r_ = dequantize_blockwise(self.exp_avg_sq_q, self.exp_avg_sq_absmax, n)
+        m_ = m_.mul(self.beta1).add(g.mul(1.0 - self.beta1))
+        v_ = r_.mul(r_).mul(self.beta2).add(g.mul(g).mul(1.0 - self.beta2))
+        denom = _sqrt_rn(v_.mul(inv_bc2)).add(self.eps)
+        w = self.master if self.master is not None else self.flat_param
+        upd = m_.mul(inv_bc1).div(denom).add(w.mul(self.weight_decay))
+        w.copy_(w.sub(upd.mul(self.lr)))
+        if self.master is not None:
+            self.flat_param.copy_(self.master.to(self.flat_param.dtype))
+        q, a = quantize_blockwise(m_)
+        self.exp_avg_q.copy_(q)
+        self.exp_avg_absmax.copy_(a)
+        q, a = quantize_blockwise(_sqrt_rn(v_))
+        self.exp_avg_sq_q.copy_(q)
+        self.exp_avg_sq_absmax.copy_(a)
+
+    def state_nbytes(self) -> int:
+        """Bytes held in moment state: codes + scales, or the two fp32 arenas."""
+        if self.state_bits == 8:
+            ts = (self.exp_avg_q, self.exp_avg_absmax,
+                  self.exp_avg_sq_q, self.exp_avg_sq_absmax)
+        else:
+            ts = (self.exp_avg, self.exp_avg_sq)
+        return sum(t.numel() * t.element_size() for t in ts)
 
     @torch.no_grad()
     def step_dev(self, lr: float | None = None):
@@ -249,6 +400,20 @@ class FusedAdamW:
 
     # -- checkpointing -----------------------------------------------------
     def state_dict(self):
+        if self.state_bits == 8:
+            d = {
+                "step": self.step_count,
+                "lr": self.lr,
+                "flat_param": self.flat_param,
+                "exp_avg_q": self.exp_avg_q,
+                "exp_avg_absmax": self.exp_avg_absmax,
+                "exp_avg_sq_q": self.exp_avg_sq_q,
+                "exp_avg_sq_absmax": self.exp_avg_sq_absmax,
+                "format": dict(STATE_FORMAT),
+            }
+            if self.master is not None:
+                d["master"] = self.master
+            return d
         d = {
             "step": self.step_count,
             "lr": self.lr,
@@ -262,11 +427,74 @@ class FusedAdamW:
             d["hyper"] = self.hyper
         return d
 
+    def _check_8bit_sd(self, sd):
+        """Validate a checkpoint when either side holds 8-bit state; raises
+        ValueError before anything is modified."""
+        n, nb = self.numel, _nblocks(self.numel)
+        fmt = sd.get("format")
+        if sd["flat_param"].numel() != n:
+            raise ValueError(
+                f"FusedAdamW.load_state_dict: checkpoint has "
+                f"{sd['flat_param'].numel()} params, optimizer has {n}")
+        if "master" in sd and sd["master"].numel() != n:
+            raise ValueError("FusedAdamW.load_state_dict: master numel mismatch")
+        if fmt is None:
+            for k in ("exp_avg", "exp_avg_sq"):
+                if k not in sd or sd[k].numel() != n:
+                    raise ValueError(
+                        f"FusedAdamW.load_state_dict: fp32-state checkpoint "
+                        f"needs '{k}' of {n} elements")
+            return
+        if fmt.get("codec") != STATE_FORMAT["codec"]:
+            raise ValueError(f"FusedAdamW.load_state_dict: unknown codec "
+                             f"{fmt.get('codec')!r}")
+        if fmt.get("qblock") != QBLOCK:
+            raise ValueError(f"FusedAdamW.load_state_dict: unknown qblock "
+                             f"{fmt.get('qblock')!r}")
+        if fmt.get("state_bits") != 8 or \
+                fmt.get("second_moment") != STATE_FORMAT["second_moment"]:
+            raise ValueError(f"FusedAdamW.load_state_dict: unknown state "
+                             f"format {fmt!r}")
+        for k, want in (("exp_avg_q", nb * QBLOCK), ("exp_avg_absmax", nb),
+                        ("exp_avg_sq_q", nb * QBLOCK), ("exp_avg_sq_absmax", nb)):
+            if k not in sd or sd[k].numel() != want:
+                raise ValueError(
+                    f"FusedAdamW.load_state_dict: '{k}' must hold {want} "
+                    f"elements for numel {n}")
+
+    def _load_moments(self, sd):
+        fmt = sd.get("format")
+        if self.state_bits == 8:
+            if fmt is not None:            # 8 -> 8: copy
+                for k in ("exp_avg_q", "exp_avg_absmax",
+                          "exp_avg_sq_q", "exp_avg_sq_absmax"):
+                    getattr(self, k).copy_(sd[k])
+            else:                          # 32 -> 8: quantise (v as sqrt)
+                q, a = quantize_blockwise(sd["exp_avg"].cpu())
+                self.exp_avg_q.copy_(q)
+                self.exp_avg_absmax.copy_(a)
+                q, a = quantize_blockwise(_sqrt_rn(sd["exp_avg_sq"].cpu().float()))
+                self.exp_avg_sq_q.copy_(q)
+                self.exp_avg_sq_absmax.copy_(a)
+        else:                              # 8 -> 32: dequantise, v = r*r
+            self.exp_avg.copy_(dequantize_blockwise(
+                sd["exp_avg_q"].cpu(), sd["exp_avg_absmax"].cpu(), self.numel))
+            r = dequantize_blockwise(
+                sd["exp_avg_sq_q"].cpu(), sd["exp_avg_sq_absmax"].cpu(), self.numel)
+            self.exp_avg_sq.copy_(r * r)
+
+    @torch.no_grad()
     def load_state_dict(self, sd):
-        self.step_count = sd["step"]
-        self.lr = sd["lr"]
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.state_bits == 8 or sd.get("format") is not None:
+            self._check_8bit_sd(sd)
+            self.step_count = sd["step"]
+            self.lr = sd["lr"]
+            self._load_moments(sd)
+        else:
+            self.step_count = sd["step"]
+            self.lr = sd["lr"]
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.flat_param.copy_(sd["flat_param"])
         if self.hyper is not None and "hyper" in sd:
             self.hyper.copy_(sd["hyper"])

@@ -272,6 +272,66 @@ void adamw_step_dev(at::Tensor p, at::Tensor g, c10::optional<at::Tensor> master
                    (float)max_norm, hyper.data_ptr<float>(), cur_stream());
 }
 
+// AdamW with block-scaled FP8 state (adamw8.hip; format in ops/hip/README.md).
+// State: codes uint8[nblocks*256] + absmax float[nblocks] per moment,
+// nblocks = ceil(numel/256).
+static void adamw8_check_state(const at::Tensor& p, const at::Tensor& mq,
+                               const at::Tensor& mabs, const at::Tensor& rq,
+                               const at::Tensor& rabs) {
+  const int64_t n = p.numel();
+  const int64_t nblocks = (n + 255) / 256;
+  TORCH_CHECK(mq.is_cuda() && mabs.is_cuda() && rq.is_cuda() && rabs.is_cuda(),
+              "adamw8: state must be on the GPU");
+  TORCH_CHECK(mq.scalar_type() == at::kByte && rq.scalar_type() == at::kByte,
+              "adamw8: codes must be uint8");
+  TORCH_CHECK(mabs.scalar_type() == at::kFloat &&
+              rabs.scalar_type() == at::kFloat, "adamw8: absmax must be fp32");
+  TORCH_CHECK(mq.is_contiguous() && mabs.is_contiguous() &&
+              rq.is_contiguous() && rabs.is_contiguous(),
+              "adamw8: state must be contiguous");
+  TORCH_CHECK(mq.numel() == nblocks * 256 && rq.numel() == nblocks * 256,
+              "adamw8: codes must hold nblocks*256 = ", nblocks * 256,
+              " bytes for numel ", n);
+  TORCH_CHECK(mabs.numel() == nblocks && rabs.numel() == nblocks,
+              "adamw8: absmax must hold nblocks = ", nblocks, " floats");
+}
+
+void adamw8_step(at::Tensor p, at::Tensor g, at::Tensor mq, at::Tensor mabs,
+                 at::Tensor rq, at::Tensor rabs, double lr, double beta1,
+                 double beta2, double eps, double wd, int64_t step) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat,
+              "adamw8: fp32 flat params expected");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat &&
+              g.numel() == p.numel(), "adamw8: fp32 grads of the same numel");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous(),
+              "adamw8: arenas must be contiguous");
+  adamw8_check_state(p, mq, mabs, rq, rabs);
+  adamw8_launch(0, p.data_ptr(), g.data_ptr(), nullptr,
+                mq.data_ptr<uint8_t>(), mabs.data_ptr<float>(),
+                rq.data_ptr<uint8_t>(), rabs.data_ptr<float>(), p.numel(), lr,
+                beta1, beta2, eps, wd, step, cur_stream());
+}
+
+void adamw8_step_bf16(at::Tensor p, at::Tensor g, at::Tensor master,
+                      at::Tensor mq, at::Tensor mabs, at::Tensor rq,
+                      at::Tensor rabs, double lr, double beta1, double beta2,
+                      double eps, double wd, int64_t step) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kBFloat16,
+              "adamw8_bf16: bf16 flat params expected");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kBFloat16 &&
+              g.numel() == p.numel(), "adamw8_bf16: bf16 grads of the same numel");
+  TORCH_CHECK(master.is_cuda() && master.scalar_type() == at::kFloat &&
+              master.numel() == p.numel(),
+              "adamw8_bf16: fp32 master of the same numel");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && master.is_contiguous(),
+              "adamw8_bf16: arenas must be contiguous");
+  adamw8_check_state(p, mq, mabs, rq, rabs);
+  adamw8_launch(1, p.data_ptr(), g.data_ptr(), master.data_ptr<float>(),
+                mq.data_ptr<uint8_t>(), mabs.data_ptr<float>(),
+                rq.data_ptr<uint8_t>(), rabs.data_ptr<float>(), p.numel(), lr,
+                beta1, beta2, eps, wd, step, cur_stream());
+}
+
 // ------------------------------------------------------------- scheduler math
 static at::Tensor sched_common(int mode, at::Tensor a, at::Tensor b, at::Tensor ac,
                                at::Tensor t) {
@@ -681,6 +741,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adamw_step", &adamw_step);
   mod.def("adamw_step_bf16", &adamw_step_bf16);
   mod.def("adamw_step_dev", &adamw_step_dev);
+  mod.def("adamw8_step", &adamw8_step, py::arg("p"), py::arg("g"),
+          py::arg("exp_avg_q"), py::arg("exp_avg_absmax"),
+          py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_absmax"), py::arg("lr"),
+          py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+          py::arg("step"));
+  mod.def("adamw8_step_bf16", &adamw8_step_bf16, py::arg("p"), py::arg("g"),
+          py::arg("master"), py::arg("exp_avg_q"), py::arg("exp_avg_absmax"),
+          py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_absmax"), py::arg("lr"),
+          py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+          py::arg("step"));
   mod.def("add_noise", &add_noise);
   mod.def("get_velocity", &get_velocity);
   mod.def("cfg_combine", &cfg_combine);

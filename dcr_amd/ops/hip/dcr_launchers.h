@@ -55,6 +55,12 @@ void adamw_dev_launch(int bf16, void* p, const void* g, float* master,
                       float* m, float* v, long n, float b1, float b2,
                       float eps, float wd, float max_norm, float* hyper,
                       hipStream_t s);
+// adamw8.hip — AdamW with block-scaled FP8 (e4m3fn) state; bf16 != 0:
+// bf16 params + fp32 master, else fp32 params (master unused).
+void adamw8_launch(int bf16, void* p, const void* g, float* master,
+                   unsigned char* mq, float* mabs, unsigned char* rq,
+                   float* rabs, long n, double lr, double b1, double b2,
+                   double eps, double wd, long step, hipStream_t s);
 void sched_launch(DType dt, int mode, const void* x0, const void* noise,
                   const float* ac, const long* t, void* out, long per_sample,
                   long total, hipStream_t s);

@@ -7,6 +7,7 @@ back out of the path, so the format is a compatibility contract).
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, asdict
 from typing import Optional
 
@@ -55,6 +56,7 @@ class TrainConfig:
     adam_weight_decay: float = 1e-2
     adam_epsilon: float = 1e-8
     max_grad_norm: float = 1.0
+    use_8bit_adam: bool = False             # block-scaled FP8 AdamW moments
     mixed_precision: str = "bf16"           # no | fp16 | bf16 | pure_bf16
     channels_last: bool = False             # NHWC convs (MI355X igemm path)
     seed: Optional[int] = None
@@ -105,6 +107,10 @@ def validate(cfg: TrainConfig):
             "Duplicating just the image in original captions scenario is not acceptable")
     if cfg.trainspecial and cfg.class_prompt != "instancelevel_blip":
         raise Exception("Cant train special without blip captions")
+    if cfg.use_8bit_adam and os.environ.get("DCR_DEV_ADAMW") == "1":
+        raise ValueError(
+            "--use_8bit_adam cannot be combined with DCR_DEV_ADAMW=1: the "
+            "device-state AdamW step has no 8-bit variant")
 
 
 def get_lr(cfg: TrainConfig, step: int, world_size: int = 1) -> float:

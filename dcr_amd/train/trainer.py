@@ -214,7 +214,8 @@ class Trainer:
             params, lr=lr, betas=(cfg.adam_beta1, cfg.adam_beta2),
             eps=cfg.adam_epsilon, weight_decay=cfg.adam_weight_decay,
             device_state=os.environ.get("DCR_DEV_ADAMW") == "1",
-            max_grad_norm=cfg.max_grad_norm)
+            max_grad_norm=cfg.max_grad_norm,
+            state_bits=8 if cfg.use_8bit_adam else 32)
         self.ddp = GradBucketAllReduce(self.optimizer, bucket_mb=cfg.ddp_bucket_mb)
 
     # ------------------------------------------------------------------
@@ -231,6 +232,9 @@ class Trainer:
         assert cfg.gradient_accumulation_steps == 1
         assert cfg.mixup_noise_lam == 0, "mixup draws host RNG per step"
         assert self.world == 1, "multi-rank capture not enabled yet"
+        assert self.optimizer.state_bits == 32, \
+            "graph capture: no device-state step for 8-bit optimizer state " \
+            "(use_8bit_adam)"
         if self.optimizer.hyper is None:
             # device-state mode: per-step scalars live on device so the
             # captured kernels read them indirectly (lr updated by a
