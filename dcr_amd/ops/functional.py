@@ -210,10 +210,36 @@ class _FlashAttention(torch.autograd.Function):
         return dQ, dK, dV, None, None
 
 
+class _FlashAttentionGen(torch.autograd.Function):
+    """bf16 flash attention for the SD-1.x head dims 40/80/160 with grad
+    (attn_fwd_gen_kernel + attn_bwd_*_gen_kernel in attention.hip).
+    q,k,v: [B, L, H, D] or packed [BH, L, D], contiguous."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, causal):
+        m = require_hip("attn_gen")
+        count_dispatch('attention_gen')
+        o, lse = m.attn_fwd_gen_lse(q, k, v, scale, causal)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale = scale
+        ctx.causal = causal
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        q, k, v, o, lse = ctx.saved_tensors
+        m = require_hip("attn_gen_bwd")
+        count_dispatch('attention_gen_bwd')
+        dQ, dK, dV = m.attn_bwd_gen(q, k, v, o, dO.contiguous(), lse,
+                                    ctx.scale, ctx.causal)
+        return dQ, dK, dV, None, None
+
+
 def _attention_math(q, k, v, scale, causal):
     """Composite path (rocBLAS GEMMs + native softmax) for shapes no HIP
-    kernel covers (now only the VAE's single 512-d head and training-mode
-    non-64 dims; SD-1.4's 40/80/160 run the gen kernel). No Triton."""
+    kernel covers: fp32 inputs, the VAE's single 512-d head, the tiny
+    config's D=32 (and 40/80/160 with grad under DCR_ATTN_GEN_BWD=0).
+    No Triton."""
     count_dispatch('attention_math')
     s = (q.float() @ k.float().transpose(-2, -1)) * scale
     if causal:
@@ -249,22 +275,32 @@ def attention(
                 v.reshape(-1, v.shape[-2], 64).contiguous(),
                 scale, causal)
             return out.reshape(shp)
+        needs_grad = torch.is_grad_enabled() and (
+            q.requires_grad or k.requires_grad or v.requires_grad)
         if q.dtype == torch.bfloat16 and q.shape[-1] in (40, 80, 160) \
-                and not (torch.is_grad_enabled() and
-                         (q.requires_grad or k.requires_grad or v.requires_grad)):
-            # SD-1.4 head dims (sd_mitigation / diff_inference sampling,
-            # reference sd_mitigation.py:46) — forward-only HIP kernel
-            m = require_hip("attn_gen")
-            count_dispatch('attention_gen')
+                and k.shape[-1] == q.shape[-1] \
+                and not (needs_grad and
+                         os.environ.get("DCR_ATTN_GEN_BWD", "1") == "0"):
+            # SD-1.x head dims: sampling (sd_mitigation / diff_inference)
+            # runs the forward kernel without an LSE; with grad the same
+            # kernel writes the LSE and the gen backward kernels follow.
+            # No length threshold: fwd+bwd measured 3.5-6.4x the composite
+            # path at every SD-1.4 bs-16 training shape, 16x16 to 4096x4096
+            # (profiles/r05_attn_gen_bwd.log). DCR_ATTN_GEN_BWD=0 sends the
+            # grad case to the composite path (A/B in one process).
+            if needs_grad:
+                fwd = lambda a, b, c: _FlashAttentionGen.apply(a, b, c, scale, causal)
+            else:
+                m = require_hip("attn_gen")
+                count_dispatch('attention_gen')
+                fwd = lambda a, b, c: m.attn_fwd_gen(a, b, c, scale, causal)
             if layout == "blhd":
-                return m.attn_fwd_gen(q.contiguous(), k.contiguous(),
-                                      v.contiguous(), scale, causal)
+                return fwd(q.contiguous(), k.contiguous(), v.contiguous())
             d = q.shape[-1]
             shp = q.shape
-            out = m.attn_fwd_gen(
-                q.reshape(-1, shp[-2], d).contiguous(),
-                k.reshape(-1, k.shape[-2], d).contiguous(),
-                v.reshape(-1, v.shape[-2], d).contiguous(), scale, causal)
+            out = fwd(q.reshape(-1, shp[-2], d).contiguous(),
+                      k.reshape(-1, k.shape[-2], d).contiguous(),
+                      v.reshape(-1, v.shape[-2], d).contiguous())
             return out.reshape(shp)
         if layout == "blhd":
             out = _attention_math(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),

@@ -1,4 +1,5 @@
-// Flash attention (forward + backward) for MI355X (gfx950), bf16, D=64.
+// Flash attention (forward + backward) for MI355X (gfx950), bf16, D=64
+// (main kernels) and D=40/80/160 (the *_gen_* kernels, SD-1.x).
 //
 // The hand-written CDNA4 FMHA required by the north star: LDS-staged
 // K/V tiles, MFMA (v_mfma_f32_16x16x32_bf16) for QK^T / PV and the
@@ -367,6 +368,8 @@ void attn_fwd_v2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__
   }
 }
 
+// D = head dim (64 for the main kernels, 40/80/160 for the gen backward)
+template <int D>
 __global__ void attn_bwd_delta_kernel(const bf16_t* __restrict__ dO,
                                       const bf16_t* __restrict__ O,
                                       float* __restrict__ delta, long total_rows,
@@ -375,12 +378,12 @@ __global__ void attn_bwd_delta_kernel(const bf16_t* __restrict__ dO,
   if (row >= total_rows) return;
   const long bh = row / Lq, l = row % Lq;
   const long b_ = bh / H, h = bh % H;
-  const long off = ((b_ * Lq + l) * H + h) * DHEAD;
+  const long off = ((b_ * Lq + l) * H + h) * D;
   const bf16_t* a = dO + off;
   const bf16_t* b = O + off;
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < DHEAD; i += 4) {
+  for (int i = 0; i < D; i += 4) {
     dcr::f32x4 av = dcr::load4<__hip_bfloat16>(a + i);
     dcr::f32x4 bv = dcr::load4<__hip_bfloat16>(b + i);
     s += av.x * bv.x + av.y * bv.y + av.z * bv.z + av.w * bv.w;
@@ -1381,9 +1384,9 @@ void attn_bwd_dkdv_v4_kernel(const bf16_t* __restrict__ q, const bf16_t* __restr
 }
 
 // ==========================================================================
-// Generalized-head-dim forward (SD-1.4 / sd_mitigation parity: head_dim
-// 40/80/160 — /root/reference/sd_mitigation.py:46; inference-only, so no
-// backward). Same tile discipline as attn_fwd_kernel with the head dim
+// Generalized-head-dim forward (SD-1.x: head_dim 40/80/160; sampling in
+// sd_mitigation / diff_inference, and the training forward when given an
+// lse pointer -- backward below). Same tile discipline as attn_fwd_kernel with the head dim
 // padded to DP = ceil(D/32)*32 (zero-padded contraction contributes 0 to
 // QK^T) and LDS pitch DP+8 bf16 — every (DP+8)*2 B row stride lands the
 // 16 rows of a ds_read_b128 lane group on 16 distinct banks (stride/4
@@ -1549,6 +1552,318 @@ void attn_fwd_gen_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict_
   }
 }
 
+// ==========================================================================
+// Generalized-head-dim backward (SD-1.x finetune: head_dim 40/80/160).
+// The v1 FlashAttention-2 split (64x64 tiles, 4 waves, no atomics: dK/dV
+// owned by key tiles, dQ by query tiles) with two changes for large D:
+//  * the wave's own 16 rows of the loop-invariant operands (K,V in dkdv;
+//    Q,dO in dq) are MFMA A fragments read once from global into
+//    registers (NK chunks x 2 operands x 4 VGPRs) instead of LDS tiles --
+//    at D=160 that takes the dkdv kernel from ~142 KB of LDS to ~97 KB;
+//  * row-major streamed tiles are zero-padded to DP (contraction chunks
+//    of 32) at pitch GP=DP+8 like the forward; transposed tiles carry
+//    only DT = ceil(D/16)*16 rows (the output d-subtiles that hold a
+//    stored column) at the v1 pitch 72.
+// ==========================================================================
+// cooperative [64 rows][DP] load, 4 threads/row, 8-element units (D%8==0):
+// row-major into dst (pitch GP) and/or transposed into dstT ([d][row]).
+template <int D, int DP, int GP, bool ROWS, bool TRANS>
+__device__ __forceinline__ void gen_load_tile(const bf16_t* __restrict__ src,
+                                              long rs, int valid,
+                                              short* __restrict__ dst,
+                                              short* __restrict__ dstT) {
+  constexpr int DT = (D + 15) / 16 * 16;
+  const int t = threadIdx.x;
+  const int row = t >> 2;
+  const bf16_t* sp_ = src + (long)row * rs;
+#pragma unroll
+  for (int c = (t & 3) * 8; c < DP; c += 32) {
+    short vv[8];
+    uint4 a = make_uint4(0, 0, 0, 0);
+    if (row < valid && c + 8 <= D)
+      a = *reinterpret_cast<const uint4*>(sp_ + c);
+    if (ROWS) *reinterpret_cast<uint4*>(dst + row * GP + c) = a;
+    if (TRANS && c < DT) {
+      *reinterpret_cast<uint4*>(vv) = a;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dstT[(c + j) * PITCH + row] = vv[j];
+    }
+  }
+}
+
+// A fragments of one sequence row straight from global: chunk ck holds
+// dims ck*32 + kgrp*8 .. +8, zero past D or for an out-of-range row.
+template <int D, int NK>
+__device__ __forceinline__ void gen_row_frags(const bf16_t* __restrict__ rowp,
+                                              bool valid, int kgrp,
+                                              bf16x8* __restrict__ f) {
+#pragma unroll
+  for (int ck = 0; ck < NK; ++ck) {
+    const int c = ck * 32 + kgrp * 8;
+    uint4 a = make_uint4(0, 0, 0, 0);
+    if (valid && c + 8 <= D) a = *reinterpret_cast<const uint4*>(rowp + c);
+    f[ck] = *reinterpret_cast<bf16x8*>(&a);
+  }
+}
+
+template <int GP>
+__device__ __forceinline__ bf16x8 frag_g(const short* lds, int row, int koff) {
+  return *reinterpret_cast<const bf16x8*>(lds + row * GP + koff);
+}
+
+// Backward dK/dV. grid (ceil(Lk/64), BH); wave owns 16 keys (K,V in regs).
+template <int D, int DP, int GP>
+__global__ __launch_bounds__(256)
+void attn_bwd_dkdv_gen_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                              const bf16_t* __restrict__ v, const bf16_t* __restrict__ dO,
+                              const float* __restrict__ lse, const float* __restrict__ delta,
+                              bf16_t* __restrict__ dK, bf16_t* __restrict__ dV,
+                              int Lq, int Lk, int H, float scale, int causal) {
+  constexpr int NK = DP / 32;             // contraction chunks over the head dim
+  constexpr int ND = (D + 15) / 16;       // output d-subtiles
+  constexpr int DT = ND * 16;
+  __shared__ short sQ[TILE * GP];        // [qrow][dim]
+  __shared__ short sdO[TILE * GP];       // [qrow][dim]
+  __shared__ short sQT[DT * PITCH];      // [dim][qrow]
+  __shared__ short sdOT[DT * PITCH];     // [dim][qrow]
+  __shared__ short sPT[TILE * PITCH];    // [key][qrow]: P^T, then dS^T
+  __shared__ float sLse[TILE];
+  __shared__ float sDelta[TILE];
+
+  const int bh = blockIdx.y;
+  const int b_ = bh / H, h = bh % H;
+  const int k0 = blockIdx.x * TILE;
+  const long rs = (long)H * D;
+  const bf16_t* qp = q + ((long)b_ * Lq * H + h) * D;
+  const bf16_t* kp = k + (((long)b_ * Lk + k0) * H + h) * D;
+  const bf16_t* vp = v + (((long)b_ * Lk + k0) * H + h) * D;
+  const bf16_t* dop = dO + ((long)b_ * Lq * H + h) * D;
+  const float* lsep = lse + (long)bh * Lq;
+  const float* delp = delta + (long)bh * Lq;
+
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int wkey0 = wid * 16;
+
+  bf16x8 kf[NK], vf[NK];
+  {
+    const int key = wkey0 + l16;
+    const bool ok = k0 + key < Lk;
+    gen_row_frags<D, NK>(kp + (long)key * rs, ok, kgrp, kf);
+    gen_row_frags<D, NK>(vp + (long)key * rs, ok, kgrp, vf);
+  }
+
+  f32x4_t acc_dk[ND], acc_dv[ND];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) {
+    acc_dk[i] = {0.f, 0.f, 0.f, 0.f};
+    acc_dv[i] = {0.f, 0.f, 0.f, 0.f};
+  }
+
+  const int q_start = causal ? k0 : 0;
+
+  for (int q0 = q_start; q0 < Lq; q0 += TILE) {
+    __syncthreads();
+    gen_load_tile<D, DP, GP, true, true>(qp + (long)q0 * rs, rs, Lq - q0, sQ, sQT);
+    gen_load_tile<D, DP, GP, true, true>(dop + (long)q0 * rs, rs, Lq - q0, sdO, sdOT);
+    if (threadIdx.x < TILE) {
+      const int qr = q0 + threadIdx.x;
+      sLse[threadIdx.x] = (qr < Lq) ? lsep[qr] : 1e30f;
+      sDelta[threadIdx.x] = (qr < Lq) ? delp[qr] : 0.f;
+    }
+    __syncthreads();
+
+    f32x4_t dst_all[4];                  // dS^T frags per query subtile
+
+#pragma unroll
+    for (int ms = 0; ms < 4; ++ms) {
+      // S^T[key][m] = K Q^T: A=K (k=dim), B=Q rows (k=dim)
+      f32x4_t st = {0.f, 0.f, 0.f, 0.f};
+      // dP^T[key][m] = V dO^T: A=V (k=dv), B=dO rows (k=dv)
+      f32x4_t dpt = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ck = 0; ck < NK; ++ck) {
+        st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            kf[ck], frag_g<GP>(sQ, ms * 16 + l16, ck * 32 + kgrp * 8), st, 0, 0, 0);
+        dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            vf[ck], frag_g<GP>(sdO, ms * 16 + l16, ck * 32 + kgrp * 8), dpt, 0, 0, 0);
+      }
+
+      const int mcol = ms * 16 + l16;
+      const float lse_m = sLse[mcol];
+      const float del_m = sDelta[mcol];
+      const int qrow = q0 + mcol;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k0 + wkey0 + kgrp * 4 + r;
+        const bool masked = (key >= Lk) || (causal && key > qrow);
+        const float pt = masked ? 0.f : __expf(st[r] * scale - lse_m);
+        sPT[(wkey0 + kgrp * 4 + r) * PITCH + mcol] = f2bf_rne(pt);
+        dst_all[ms][r] = pt * (dpt[r] - del_m) * scale;
+      }
+    }
+
+    // dV[key][dv] += P^T dO: A = P^T (k=m, sPT rows), B = dO^T rows (k=m)
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc) {
+      bf16x8 ptf = frag(sPT, wkey0 + l16, kgrp * 8 + kc * 32);
+#pragma unroll
+      for (int ds_ = 0; ds_ < ND; ++ds_)
+        acc_dv[ds_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            ptf, frag(sdOT, ds_ * 16 + l16, kgrp * 8 + kc * 32),
+            acc_dv[ds_], 0, 0, 0);
+    }
+
+    // overwrite sPT with dS^T (wave-local rows), then
+    // dK[key][dim] += dS^T Q: A = dS^T (k=m), B = Q^T rows (k=m)
+#pragma unroll
+    for (int ms = 0; ms < 4; ++ms)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        sPT[(wkey0 + kgrp * 4 + r) * PITCH + ms * 16 + l16] =
+            f2bf_rne(dst_all[ms][r]);
+
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc) {
+      bf16x8 dsf = frag(sPT, wkey0 + l16, kgrp * 8 + kc * 32);
+#pragma unroll
+      for (int ds_ = 0; ds_ < ND; ++ds_)
+        acc_dk[ds_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            dsf, frag(sQT, ds_ * 16 + l16, kgrp * 8 + kc * 32),
+            acc_dk[ds_], 0, 0, 0);
+    }
+  }
+
+  // store dK/dV rows (key- and d-guarded)
+  bf16_t* dkp = dK + (((long)b_ * Lk + k0) * H + h) * D;
+  bf16_t* dvp = dV + (((long)b_ * Lk + k0) * H + h) * D;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int key = wkey0 + kgrp * 4 + r;
+    if (k0 + key >= Lk) continue;
+#pragma unroll
+    for (int ds_ = 0; ds_ < ND; ++ds_) {
+      const int d = ds_ * 16 + l16;
+      if (d < D) {
+        dkp[(long)key * rs + d] = __float2bfloat16(acc_dk[ds_][r]);
+        dvp[(long)key * rs + d] = __float2bfloat16(acc_dv[ds_][r]);
+      }
+    }
+  }
+}
+
+// Backward dQ. grid (ceil(Lq/64), BH); wave owns 16 q rows (Q,dO in regs).
+template <int D, int DP, int GP>
+__global__ __launch_bounds__(256)
+void attn_bwd_dq_gen_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                            const bf16_t* __restrict__ v, const bf16_t* __restrict__ dO,
+                            const float* __restrict__ lse, const float* __restrict__ delta,
+                            bf16_t* __restrict__ dQ, int Lq, int Lk, int H,
+                            float scale, int causal) {
+  constexpr int NK = DP / 32;
+  constexpr int ND = (D + 15) / 16;
+  constexpr int DT = ND * 16;
+  __shared__ short sK[TILE * GP];        // [key][dim]
+  __shared__ short sV[TILE * GP];        // [key][dim]
+  __shared__ short sKT[DT * PITCH];      // [dim][key]
+  __shared__ short sDS[TILE * PITCH];    // [qrow][key]
+
+  const int bh = blockIdx.y;
+  const int b_ = bh / H, h = bh % H;
+  const int q0 = blockIdx.x * TILE;
+  const long rs = (long)H * D;
+  const bf16_t* qp = q + (((long)b_ * Lq + q0) * H + h) * D;
+  const bf16_t* kp = k + ((long)b_ * Lk * H + h) * D;
+  const bf16_t* vp = v + ((long)b_ * Lk * H + h) * D;
+  const bf16_t* dop = dO + (((long)b_ * Lq + q0) * H + h) * D;
+
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int wrow0 = wid * 16;
+
+  bf16x8 qf[NK], df[NK];
+  {
+    const int row = wrow0 + l16;
+    const bool ok = q0 + row < Lq;
+    gen_row_frags<D, NK>(qp + (long)row * rs, ok, kgrp, qf);
+    gen_row_frags<D, NK>(dop + (long)row * rs, ok, kgrp, df);
+  }
+
+  // per-lane row constants (rows m = kgrp*4 + r)
+  float lse_r[4], del_r[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qrow = q0 + wrow0 + kgrp * 4 + r;
+    lse_r[r] = (qrow < Lq) ? lse[(long)bh * Lq + qrow] : 1e30f;
+    del_r[r] = (qrow < Lq) ? delta[(long)bh * Lq + qrow] : 0.f;
+  }
+
+  f32x4_t acc_dq[ND];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) acc_dq[i] = {0.f, 0.f, 0.f, 0.f};
+
+  const int kv_end = causal ? min(Lk, q0 + TILE) : Lk;
+
+  for (int kv0 = 0; kv0 < kv_end; kv0 += TILE) {
+    __syncthreads();
+    gen_load_tile<D, DP, GP, true, true>(kp + (long)kv0 * rs, rs, Lk - kv0, sK, sKT);
+    gen_load_tile<D, DP, GP, true, false>(vp + (long)kv0 * rs, rs, Lk - kv0, sV, nullptr);
+    __syncthreads();
+
+#pragma unroll
+    for (int ns = 0; ns < 4; ++ns) {
+      // S[m][key] = Q K^T: A=Q (k=dim), B=K rows (k=dim)
+      f32x4_t s = {0.f, 0.f, 0.f, 0.f};
+      // dP[m][key] = dO V^T: A=dO (k=dv), B=V rows (k=dv)
+      f32x4_t dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ck = 0; ck < NK; ++ck) {
+        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            qf[ck], frag_g<GP>(sK, ns * 16 + l16, ck * 32 + kgrp * 8), s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            df[ck], frag_g<GP>(sV, ns * 16 + l16, ck * 32 + kgrp * 8), dp, 0, 0, 0);
+      }
+
+      const int key = kv0 + ns * 16 + l16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int qrow = q0 + wrow0 + kgrp * 4 + r;
+        const bool masked = (key >= Lk) || (causal && key > qrow);
+        const float p = masked ? 0.f : __expf(s[r] * scale - lse_r[r]);
+        sDS[(wrow0 + kgrp * 4 + r) * PITCH + ns * 16 + l16] =
+            f2bf_rne(p * (dp[r] - del_r[r]) * scale);
+      }
+    }
+
+    // dQ[m][dim] += dS K: A = dS (k=key, sDS rows), B = K^T rows (k=key)
+#pragma unroll
+    for (int kc = 0; kc < 2; ++kc) {
+      bf16x8 dsf = frag(sDS, wrow0 + l16, kgrp * 8 + kc * 32);
+#pragma unroll
+      for (int ds_ = 0; ds_ < ND; ++ds_)
+        acc_dq[ds_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            dsf, frag(sKT, ds_ * 16 + l16, kgrp * 8 + kc * 32),
+            acc_dq[ds_], 0, 0, 0);
+    }
+  }
+
+  bf16_t* dqp = dQ + (((long)b_ * Lq + q0) * H + h) * D;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = wrow0 + kgrp * 4 + r;
+    if (q0 + row >= Lq) continue;
+#pragma unroll
+    for (int ds_ = 0; ds_ < ND; ++ds_) {
+      const int d = ds_ * 16 + l16;
+      if (d < D) dqp[(long)row * rs + d] = __float2bfloat16(acc_dq[ds_][r]);
+    }
+  }
+}
+
 }  // namespace dcr_attn
 
 // ==========================================================================
@@ -1608,7 +1923,7 @@ void attn_bwd_launch(const void* q, const void* k, const void* v,
                      hipStream_t s) {
   long rows = (long)BH * Lq;
   dim3 gd((rows + 255) / 256), bd(256);
-  hipLaunchKernelGGL(dcr_attn::attn_bwd_delta_kernel, gd, bd, 0, s,
+  hipLaunchKernelGGL(dcr_attn::attn_bwd_delta_kernel<DHEAD>, gd, bd, 0, s,
                      (const dcr_attn::bf16_t*)dO, (const dcr_attn::bf16_t*)o,
                      delta, rows, Lq, H);
   dim3 g1((Lk + TILE - 1) / TILE, BH), b1(256);
@@ -1625,7 +1940,7 @@ void attn_bwd_launch(const void* q, const void* k, const void* v,
                      causal ? 1 : 0);
 }
 
-// generalized head-dim forward (SD-1.4 40/80/160; inference-only)
+// generalized head-dim forward (SD-1.x 40/80/160); lse may be nullptr
 void attn_fwd_gen_launch(const void* q, const void* k, const void* v, void* o,
                          float* lse, int BH, int Lq, int Lk, int H, int D,
                          float scale, bool causal, hipStream_t s) {
@@ -1653,6 +1968,56 @@ void attn_fwd_gen_launch(const void* q, const void* k, const void* v, void* o,
   }
 }
 
+// generalized head-dim backward (SD-1.x finetune 40/80/160): delta, then
+// dK/dV per key tile and dQ per query tile -- no atomics, deterministic
+template <int D, int DP, int GP>
+static void attn_bwd_gen_launch_t(const dcr_attn::bf16_t* q, const dcr_attn::bf16_t* k,
+                                  const dcr_attn::bf16_t* v, const dcr_attn::bf16_t* o,
+                                  const dcr_attn::bf16_t* dO, const float* lse,
+                                  float* delta, dcr_attn::bf16_t* dQ,
+                                  dcr_attn::bf16_t* dK, dcr_attn::bf16_t* dV,
+                                  int BH, int Lq, int Lk, int H, float scale,
+                                  int causal, hipStream_t s) {
+  long rows = (long)BH * Lq;
+  dim3 gd((rows + 255) / 256), bd(256);
+  hipLaunchKernelGGL(dcr_attn::attn_bwd_delta_kernel<D>, gd, bd, 0, s, dO, o,
+                     delta, rows, Lq, H);
+  dim3 g1((Lk + TILE - 1) / TILE, BH), b1(256);
+  hipLaunchKernelGGL((dcr_attn::attn_bwd_dkdv_gen_kernel<D, DP, GP>), g1, b1, 0,
+                     s, q, k, v, dO, lse, delta, dK, dV, Lq, Lk, H, scale, causal);
+  dim3 g2((Lq + TILE - 1) / TILE, BH), b2(256);
+  hipLaunchKernelGGL((dcr_attn::attn_bwd_dq_gen_kernel<D, DP, GP>), g2, b2, 0,
+                     s, q, k, v, dO, lse, delta, dQ, Lq, Lk, H, scale, causal);
+}
+
+void attn_bwd_gen_launch(const void* q, const void* k, const void* v,
+                         const void* o, const void* dO, const float* lse,
+                         float* delta, void* dQ, void* dK, void* dV, int BH,
+                         int Lq, int Lk, int H, int D, float scale,
+                         bool causal, hipStream_t s) {
+  using T = dcr_attn::bf16_t;
+  const int c = causal ? 1 : 0;
+  switch (D) {
+    case 40:
+      attn_bwd_gen_launch_t<40, 64, 72>(
+          (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dO, lse,
+          delta, (T*)dQ, (T*)dK, (T*)dV, BH, Lq, Lk, H, scale, c, s);
+      break;
+    case 80:
+      attn_bwd_gen_launch_t<80, 96, 104>(
+          (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dO, lse,
+          delta, (T*)dQ, (T*)dK, (T*)dV, BH, Lq, Lk, H, scale, c, s);
+      break;
+    case 160:
+      attn_bwd_gen_launch_t<160, 160, 168>(
+          (const T*)q, (const T*)k, (const T*)v, (const T*)o, (const T*)dO, lse,
+          delta, (T*)dQ, (T*)dK, (T*)dV, BH, Lq, Lk, H, scale, c, s);
+      break;
+    default:
+      break;  // binding guards D
+  }
+}
+
 // backward v4 (swapped-operand schedule; DCR_ATTN_BWD_V4 draft)
 void attn_bwd_v4_launch(const void* q, const void* k, const void* v,
                         const void* o, const void* dO, const float* lse,
@@ -1661,7 +2026,7 @@ void attn_bwd_v4_launch(const void* q, const void* k, const void* v,
                         hipStream_t s) {
   long rows = (long)BH * Lq;
   dim3 gd((rows + 255) / 256), bd(256);
-  hipLaunchKernelGGL(dcr_attn::attn_bwd_delta_kernel, gd, bd, 0, s,
+  hipLaunchKernelGGL(dcr_attn::attn_bwd_delta_kernel<DHEAD>, gd, bd, 0, s,
                      (const dcr_attn::bf16_t*)dO, (const dcr_attn::bf16_t*)o,
                      delta, rows, Lq, H);
   dim3 g1((Lk + 255) / 256, BH), b1(512);

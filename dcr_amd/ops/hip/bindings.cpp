@@ -419,17 +419,17 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   return {o, lse};
 }
 
-// generalized head-dim forward (SD-1.4 40/80/160; inference-only — no
-// backward: sd_mitigation / diff_inference sampling runs under no_grad)
-at::Tensor attn_fwd_gen(at::Tensor q, at::Tensor k, at::Tensor v,
-                        double scale, bool causal) {
+// generalized head-dim kernels (SD-1.x 40/80/160). q/k/v: [B, L, H, D]
+// or packed [BH, L, D].
+static void attn_gen_dims(const at::Tensor& q, const at::Tensor& k,
+                          const at::Tensor& v, int64_t& B, int64_t& H,
+                          int64_t& Lq, int64_t& Lk, int64_t& D) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16,
               "attn_gen: bf16 CUDA only");
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
-  const int64_t D = q.size(-1);
+  D = q.size(-1);
   TORCH_CHECK(D == 40 || D == 80 || D == 160,
               "attn_gen: head_dim 40/80/160 only (64 has the main kernel)");
-  int64_t B, H, Lq, Lk;
   if (q.dim() == 4) {
     B = q.size(0); Lq = q.size(1); H = q.size(2); Lk = k.size(1);
     TORCH_CHECK(k.dim() == 4 && k.size(2) == H && k.size(-1) == D);
@@ -437,11 +437,67 @@ at::Tensor attn_fwd_gen(at::Tensor q, at::Tensor k, at::Tensor v,
     TORCH_CHECK(q.dim() == 3);
     B = q.size(0); Lq = q.size(1); H = 1; Lk = k.size(1);
   }
+}
+
+static at::Tensor attn_fwd_gen_impl(const at::Tensor& q, const at::Tensor& k,
+                                    const at::Tensor& v, double scale,
+                                    bool causal, at::Tensor* lse) {
+  int64_t B, H, Lq, Lk, D;
+  attn_gen_dims(q, k, v, B, H, Lq, Lk, D);
   auto o = at::empty_like(q);
+  float* lse_p = nullptr;
+  if (lse != nullptr) {
+    *lse = at::empty({B * H, Lq}, q.options().dtype(at::kFloat));
+    lse_p = lse->data_ptr<float>();
+  }
   attn_fwd_gen_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                      nullptr, (int)(B * H), (int)Lq, (int)Lk, (int)H, (int)D,
+                      lse_p, (int)(B * H), (int)Lq, (int)Lk, (int)H, (int)D,
                       (float)scale, causal, cur_stream());
   return o;
+}
+
+// forward without LSE (sampling under no_grad)
+at::Tensor attn_fwd_gen(at::Tensor q, at::Tensor k, at::Tensor v,
+                        double scale, bool causal) {
+  return attn_fwd_gen_impl(q, k, v, scale, causal, nullptr);
+}
+
+// training forward: same kernel, also writes lse [B*H, Lq] fp32
+std::vector<at::Tensor> attn_fwd_gen_lse(at::Tensor q, at::Tensor k,
+                                         at::Tensor v, double scale,
+                                         bool causal) {
+  at::Tensor lse;
+  auto o = attn_fwd_gen_impl(q, k, v, scale, causal, &lse);
+  return {o, lse};
+}
+
+std::vector<at::Tensor> attn_bwd_gen(at::Tensor q, at::Tensor k, at::Tensor v,
+                                     at::Tensor o, at::Tensor dO,
+                                     at::Tensor lse, double scale,
+                                     bool causal) {
+  int64_t B, H, Lq, Lk, D;
+  attn_gen_dims(q, k, v, B, H, Lq, Lk, D);
+  TORCH_CHECK(k.sizes() == v.sizes(), "attn_bwd_gen: k/v shape mismatch");
+  TORCH_CHECK(o.sizes() == q.sizes() && dO.sizes() == q.sizes(),
+              "attn_bwd_gen: o/dO must have q's shape");
+  TORCH_CHECK(o.is_cuda() && dO.is_cuda() && lse.is_cuda() &&
+              o.scalar_type() == at::kBFloat16 &&
+              dO.scalar_type() == at::kBFloat16 &&
+              o.is_contiguous() && dO.is_contiguous(),
+              "attn_bwd_gen: o/dO must be contiguous bf16 CUDA tensors");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.dim() == 2 && lse.size(0) == B * H && lse.size(1) == Lq,
+              "attn_bwd_gen: lse must be contiguous fp32 [B*H, Lq]");
+  auto dQ = at::empty_like(q);
+  auto dK = at::empty_like(k);
+  auto dV = at::empty_like(v);
+  auto delta = at::empty({B * H, Lq}, q.options().dtype(at::kFloat));
+  attn_bwd_gen_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                      dO.data_ptr(), lse.data_ptr<float>(),
+                      delta.data_ptr<float>(), dQ.data_ptr(), dK.data_ptr(),
+                      dV.data_ptr(), (int)(B * H), (int)Lq, (int)Lk, (int)H,
+                      (int)D, (float)scale, causal, cur_stream());
+  return {dQ, dK, dV};
 }
 
 // round-2 draft: T14 async K/V staging + one barrier per tile + setprio
@@ -724,6 +780,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("temb") = c10::nullopt);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_fwd_gen", &attn_fwd_gen);
+  mod.def("attn_fwd_gen_lse", &attn_fwd_gen_lse);
+  mod.def("attn_bwd_gen", &attn_bwd_gen);
   mod.def("attn_fwd_v2", &attn_fwd_v2);
   mod.def("attn_fwd_v3", &attn_fwd_v3);
   mod.def("attn_fwd_v4", &attn_fwd_v4);

@@ -86,10 +86,16 @@ void attn_fwd_v3_launch(const void* q, const void* k, const void* v, void* o,
 void attn_fwd_v4_launch(const void* q, const void* k, const void* v, void* o,
                         float* lse, int BH, int Lq, int Lk, int H, float scale,
                         bool causal, hipStream_t s);
-// generalized head-dim forward (SD-1.4 40/80/160; inference-only)
+// generalized head-dim forward (SD-1.x 40/80/160); lse may be nullptr
 void attn_fwd_gen_launch(const void* q, const void* k, const void* v, void* o,
                          float* lse, int BH, int Lq, int Lk, int H, int D,
                          float scale, bool causal, hipStream_t s);
+// generalized head-dim backward (40/80/160): delta + dK/dV + dQ, no atomics
+void attn_bwd_gen_launch(const void* q, const void* k, const void* v,
+                         const void* o, const void* dO, const float* lse,
+                         float* delta, void* dQ, void* dK, void* dV, int BH,
+                         int Lq, int Lk, int H, int D, float scale,
+                         bool causal, hipStream_t s);
 void attn_bwd_launch(const void* q, const void* k, const void* v,
                      const void* o, const void* dO, const float* lse,
                      float* delta, void* dQ, void* dK, void* dV, int BH,

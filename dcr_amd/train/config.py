@@ -20,7 +20,7 @@ class TrainConfig:
     tokenizer_name: Optional[str] = None    # explicit tokenizer dir (diff_train.py:371)
     unet_from_scratch: str = "no"          # 'yes' => random-init UNet (BASELINE path)
     unet_config: Optional[str] = None       # ./unet_config.json when from scratch
-    model_size: str = "sd21"                # sd21 | tiny (tiny = CPU tests)
+    model_size: str = "sd21"                # sd21 | sd14 | tiny (tiny = CPU tests)
     train_text_encoder: bool = False
     prediction_type: Optional[str] = None   # override scheduler (epsilon/v_prediction)
 

@@ -33,8 +33,8 @@ from torch.utils.data.distributed import DistributedSampler
 
 from ..data import (HashTokenizer, ObjectAttributeDataset, SyntheticImageDataset,
                     collate_fn, load_tokenizer)
-from ..models import (AutoencoderKL, CLIPTextModel, CLIPTextConfig,
-                      UNet2DConditionModel, UNetConfig, VAEConfig)
+from ..models import (AutoencoderKL, CLIPTextModel, UNet2DConditionModel,
+                      UNetConfig, model_configs)
 from ..models.model_io import save_pipeline_index
 from ..ops.adamw import FusedAdamW
 from ..parallel import GradBucketAllReduce, dist as dist_utils
@@ -105,10 +105,7 @@ class Trainer:
             self.tokenizer = load_tokenizer(pretrained / "tokenizer")
         else:
             # no network: random-init models of the named architecture
-            if cfg.model_size == "tiny":
-                ucfg, vcfg, tcfg = UNetConfig.tiny(), VAEConfig.tiny(), CLIPTextConfig.tiny()
-            else:
-                ucfg, vcfg, tcfg = UNetConfig.sd21(), VAEConfig.sd(), CLIPTextConfig.sd21()
+            ucfg, vcfg, tcfg = model_configs(cfg.model_size)
             if cfg.unet_from_scratch == "yes" and cfg.unet_config:
                 ucfg = UNetConfig.from_json(Path(cfg.unet_config).read_text())
             self.unet = UNet2DConditionModel(ucfg)

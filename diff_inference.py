@@ -160,14 +160,11 @@ def main(args):
         pipe = StableDiffusionPipeline.from_pretrained(
             checkpath, embed_noise_lam=args.rand_noise_lam or 0.0)
     else:
-        # stock model path: no weights on disk -> random-init SD-2.1 arch
-        from dcr_amd.models import (AutoencoderKL, CLIPTextModel, CLIPTextConfig,
-                                    UNet2DConditionModel, UNetConfig, VAEConfig)
+        # stock model path: no weights on disk -> random-init named arch
+        from dcr_amd.models import (AutoencoderKL, CLIPTextModel,
+                                    UNet2DConditionModel, model_configs)
         from dcr_amd.data.tokenizer import HashTokenizer
-        size = args.model_size
-        ucfg = UNetConfig.tiny() if size == "tiny" else UNetConfig.sd21()
-        vcfg = VAEConfig.tiny() if size == "tiny" else VAEConfig.sd()
-        tcfg = CLIPTextConfig.tiny() if size == "tiny" else CLIPTextConfig.sd21()
+        ucfg, vcfg, tcfg = model_configs(args.model_size)
         pipe = StableDiffusionPipeline(
             UNet2DConditionModel(ucfg), AutoencoderKL(vcfg), CLIPTextModel(tcfg),
             HashTokenizer(), DPMSolverMultistepScheduler(),
@@ -222,7 +219,7 @@ if __name__ == "__main__":
     parser.add_argument("--seed", type=int, default=42)
     parser.add_argument("--prompt_json", type=str, default=None)
     parser.add_argument("--model_size", type=str, default="sd21",
-                        choices=["sd21", "tiny"])
+                        choices=["sd21", "sd14", "tiny"])
     args = parser.parse_args()
 
     assert not (args.modelpath is None and args.capstyle is None), \

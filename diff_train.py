@@ -88,7 +88,7 @@ def parse_args(argv=None):
                    choices=["no", "yes"])
     p.add_argument("--unet_config", type=str, default="./unet_config.json")
     p.add_argument("--model_size", type=str, default="sd21",
-                   choices=["sd21", "tiny"],
+                   choices=["sd21", "sd14", "tiny"],
                    help="architecture family when weights are not local")
     p.add_argument("--synthetic_data", action="store_true",
                    help="random images/captions instead of instance_data_dir")

@@ -42,12 +42,10 @@ def main(args):
             embed_noise_lam=args.rand_noise_lam or 0.0)
         tokenizer = pipe.tokenizer
     else:
-        from dcr_amd.models import (AutoencoderKL, CLIPTextModel, CLIPTextConfig,
-                                    UNet2DConditionModel, UNetConfig, VAEConfig)
-        if args.model_size == "tiny":
-            ucfg, vcfg, tcfg = UNetConfig.tiny(), VAEConfig.tiny(), CLIPTextConfig.tiny()
-        else:  # SD-1.4 (reference checkpath CompVis/stable-diffusion-v1-4)
-            ucfg, vcfg, tcfg = UNetConfig.sd14(), VAEConfig.sd(), CLIPTextConfig.sd14()
+        from dcr_amd.models import (AutoencoderKL, CLIPTextModel,
+                                    UNet2DConditionModel, model_configs)
+        # default sd14 (reference checkpath CompVis/stable-diffusion-v1-4)
+        ucfg, vcfg, tcfg = model_configs(args.model_size)
         tokenizer = HashTokenizer()
         pipe = StableDiffusionPipeline(
             UNet2DConditionModel(ucfg), AutoencoderKL(vcfg), CLIPTextModel(tcfg),
