@@ -22,6 +22,7 @@ SOURCES = [
     HIP_DIR / "norms.hip",
     HIP_DIR / "norms_nhwc.hip",
     HIP_DIR / "elementwise.hip",
+    HIP_DIR / "reduce.hip",
     HIP_DIR / "adamw8.hip",
     HIP_DIR / "attention.hip",
     HIP_DIR / "conv_nhwc.hip",

@@ -10,6 +10,10 @@ Eligibility (checked per call): CUDA bf16 channels_last input+weight,
 C % 32 == 0, K % 64 == 0, 3x3(pad 1, dil 1) or 1x1(pad 0), stride 1|2,
 no groups. Anything else falls through to torch's conv. Opt out with
 DCR_NATIVE_CONV=0.
+
+The backward asks MIOpen for dx and dw only; the bias gradient, and d_temb
+when a time embedding was fused, come from reduce.hip's column sums in one
+read of dy. DCR_NATIVE_BIAS_GRAD=0 (read per call) restores the aten sums.
 """
 from __future__ import annotations
 
@@ -24,6 +28,10 @@ from . import count_dispatch, ext
 
 def _enabled() -> bool:
     return os.environ.get("DCR_NATIVE_CONV", "1") != "0"
+
+
+def _bias_grad_enabled() -> bool:
+    return os.environ.get("DCR_NATIVE_BIAS_GRAD", "1") != "0"
 
 
 def _eligible(x: torch.Tensor, m: nn.Conv2d) -> bool:
@@ -76,6 +84,25 @@ class _NativeConvFn(torch.autograd.Function):
         stride, padding, has_bias, has_res, has_temb = ctx.conf
         dy = dy.contiguous(memory_format=torch.channels_last)
         d_res = dy if has_res else None
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if _bias_grad_enabled() and (want_db or has_temb) \
+                and os.environ.get("DCR_NATIVE_CONV_BWD", "0") != "1":
+            # reduce.hip: dbias (and d_temb, from the same read of dy) as
+            # column sums of the NHWC dy seen as [N, P*Q, K]
+            m = ext()
+            count_dispatch('bias_grad')
+            n, k = dy.shape[0], dy.shape[1]
+            dy3 = dy.permute(0, 2, 3, 1).reshape(n, -1, k)
+            if has_temb:
+                d_temb, db = m.colsum_grouped(dy3)
+            else:
+                d_temb, db = None, m.colsum(dy3.view(-1, k))
+            dx, dw, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight, None,
+                [stride, stride], [padding, padding], [1, 1], False, [0, 0],
+                1, [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False])
+            return dx, dw, (db if want_db else None), None, None, d_res, \
+                d_temb
         d_temb = dy.sum(dim=(2, 3)) if has_temb else None
         # native backward (conv_nhwc_bwd.hip: dgrad + wgrad + fused
         # bias-grad) — numerics GPU-validated round 2; C % 64 shapes only

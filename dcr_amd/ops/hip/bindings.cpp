@@ -137,23 +137,20 @@ std::vector<at::Tensor> groupnorm_silu_nhwc_bwd(at::Tensor dy, at::Tensor x,
   auto dx = at::empty_like(x);
   const int64_t chunks = gn_nhwc_chunks((int)N, (int)R);
   // [chunk-partial group sums | chunk-partial dw/db | finalized groups]
-  // — every slot plain-stored, so no zero-init kernel; dw/db are the
-  // finalize kernel's outputs
-  auto scratch = at::empty(
-      {chunks * N * groups * 2 + chunks * N * 2 * C + N * groups * 2 + 2 * C},
+  // — every slot plain-stored, so no zero-init kernel. The finalize
+  // kernel writes dw|db in the weight dtype: stats, finalize, apply.
+  TORCH_CHECK(wf32 == bf32);
+  auto ws = at::empty(
+      {chunks * N * groups * 2 + chunks * N * 2 * C + N * groups * 2},
       x.options().dtype(at::kFloat));
-  auto ws = scratch.narrow(0, 0, chunks * N * groups * 2);
-  auto dw = scratch.narrow(
-      0, chunks * N * groups * 2 + chunks * N * 2 * C + N * groups * 2, C);
-  auto db = scratch.narrow(
-      0, chunks * N * groups * 2 + chunks * N * 2 * C + N * groups * 2 + C, C);
+  auto dwdb = at::empty({2 * C}, wf.options());
   gn_nhwc_bwd_launch(dtype_of(x), dy.data_ptr(), x.data_ptr(),
                      wf.data_ptr(), bf.data_ptr(), wf32,
                      mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                     ws.data_ptr<float>(), dx.data_ptr(), dw.data_ptr<float>(),
-                     db.data_ptr<float>(), (int)N, (int)R, (int)C, (int)groups,
-                     silu, cur_stream());
-  return {dx, dw.to(w.scalar_type()), db.to(b.scalar_type())};
+                     ws.data_ptr<float>(), dx.data_ptr(), dwdb.data_ptr(),
+                     (int)N, (int)R, (int)C, (int)groups, silu, cur_stream());
+  return {dx, dwdb.narrow(0, 0, C).to(w.scalar_type()),
+          dwdb.narrow(0, C, C).to(b.scalar_type())};
 }
 
 // ---------------------------------------------------------------- LayerNorm
@@ -176,8 +173,10 @@ std::vector<at::Tensor> layernorm_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
   return {y, mean, rstd};
 }
 
+// blocks > 0 overrides the v2 grid (scripts/bench_norms.py sweeps it)
 std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
-                                      at::Tensor mean, at::Tensor rstd) {
+                                      at::Tensor mean, at::Tensor rstd,
+                                      int64_t blocks) {
   TORCH_CHECK(dy.is_contiguous() && x.is_contiguous());
   const int64_t Nd = x.size(-1);
   const int64_t M = x.numel() / Nd;
@@ -185,6 +184,19 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
   bool wf32;
   auto wf = norm_weight(w, x, wf32);
   auto dx = at::empty_like(x);
+  int64_t nblk = ln_bwd_v2_blocks(M, (int)Nd);
+  if (nblk > 0) {
+    if (blocks > 0) nblk = std::min<int64_t>(blocks, 65535);
+    // main kernel + slab reduce; dw|db leave the reduce in wf's dtype
+    auto slab = at::empty({nblk * 2 * Nd}, x.options().dtype(at::kFloat));
+    auto dwdb_t = at::empty({2 * Nd}, wf.options());
+    ln_bwd_v2_launch(dtype_of(x), dy.data_ptr(), x.data_ptr(), wf.data_ptr(),
+                     wf32, mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                     dx.data_ptr(), slab.data_ptr<float>(), dwdb_t.data_ptr(),
+                     (int)nblk, M, (int)Nd, cur_stream());
+    return {dx, dwdb_t.narrow(0, 0, Nd).to(w.scalar_type()),
+            dwdb_t.narrow(0, Nd, Nd).to(w.scalar_type())};
+  }
   auto dwdb = at::zeros({2 * Nd}, x.options().dtype(at::kFloat));
   auto dw = dwdb.narrow(0, 0, Nd);
   auto db = dwdb.narrow(0, Nd, Nd);
@@ -193,6 +205,44 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x, at::Tensor w,
                 dw.data_ptr<float>(), db.data_ptr<float>(), M, (int)Nd,
                 cur_stream());
   return {dx, dw.to(w.scalar_type()), db.to(w.scalar_type())};
+}
+
+// ------------------------------------------------------ bias-grad column sums
+// x: [rows, C] contiguous -> [C] (fp32 accumulation, x's dtype out)
+at::Tensor colsum(at::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(),
+              "colsum: contiguous CUDA [rows, C] expected");
+  const int64_t rows = x.size(0), C = x.size(1);
+  TORCH_CHECK(rows >= 1 && C >= 1 && C < (1 << 30));
+  const DType dt = dtype_of(x);
+  const int chunks = colsum_chunks((int)dt, 1, rows, (int)C, 128);
+  auto out = at::empty({C}, x.options());
+  at::Tensor slab;
+  float* sp = nullptr;
+  if (chunks > 1) {
+    slab = at::empty({chunks * C}, x.options().dtype(at::kFloat));
+    sp = slab.data_ptr<float>();
+  }
+  colsum_launch(dt, x.data_ptr(), sp, nullptr, out.data_ptr(), 1, rows, (int)C,
+                chunks, cur_stream());
+  return out;
+}
+
+// x: [N, HW, C] contiguous -> ([N, C], [C]); the [C] output is the fp32 sum
+// of the unrounded per-sample sums (d_temb and dbias from one read of dy)
+std::vector<at::Tensor> colsum_grouped(at::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous(),
+              "colsum_grouped: contiguous CUDA [N, HW, C] expected");
+  const int64_t N = x.size(0), HW = x.size(1), C = x.size(2);
+  TORCH_CHECK(N >= 1 && HW >= 1 && C >= 1 && C < (1 << 30));
+  const DType dt = dtype_of(x);
+  const int chunks = colsum_chunks((int)dt, N, HW, (int)C, 16);
+  auto out_n = at::empty({N, C}, x.options());
+  auto out = at::empty({C}, x.options());
+  auto slab = at::empty({N * chunks * C}, x.options().dtype(at::kFloat));
+  colsum_launch(dt, x.data_ptr(), slab.data_ptr<float>(), out_n.data_ptr(),
+                out.data_ptr(), N, HW, (int)C, chunks, cur_stream());
+  return {out_n, out};
 }
 
 // ---------------------------------------------------------------- GEGLU
@@ -594,6 +644,22 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 }
 
 // ---------------------------------------------------------------- conv
+// The conv kernels read the bias as bf16 or fp32 and widen it in the
+// epilogue, so the parameter goes in as it is: no cast kernel per call.
+// `keep` holds the tensor the returned pointer belongs to.
+static const void* conv_bias_ptr(const c10::optional<at::Tensor>& bias,
+                                 at::Tensor& keep, bool& is_bf16) {
+  is_bf16 = false;
+  if (!bias.has_value()) return nullptr;
+  if (bias->scalar_type() == at::kBFloat16) {
+    is_bf16 = true;
+    keep = bias->contiguous();
+  } else {
+    keep = as_f32(*bias);
+  }
+  return keep.data_ptr();
+}
+
 at::Tensor conv2d_nhwc_fwd(at::Tensor x, at::Tensor w,
                            c10::optional<at::Tensor> bias, int64_t stride,
                            int64_t pad) {
@@ -610,12 +676,9 @@ at::Tensor conv2d_nhwc_fwd(at::Tensor x, at::Tensor w,
   auto y = at::empty({Nb, K, P, Q},
                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
   at::Tensor bf;
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    bf = bias->to(at::kFloat).contiguous();
-    bp = bf.data_ptr<float>();
-  }
-  conv_nhwc_fwd_launch(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), (int)Nb,
+  bool b_bf16 = false;
+  const void* bp = conv_bias_ptr(bias, bf, b_bf16);
+  conv_nhwc_fwd_launch(x.data_ptr(), w.data_ptr(), bp, b_bf16, y.data_ptr(), (int)Nb,
                        (int)Hin, (int)Win, (int)C, (int)K, (int)P, (int)Q,
                        (int)R, (int)S, (int)stride, (int)pad, cur_stream());
   return y;
@@ -638,11 +701,8 @@ static at::Tensor conv2d_nhwc_fwd_v2_impl(at::Tensor x, at::Tensor w,
   auto y = at::empty({Nb, K, P, Q},
                      x.options().memory_format(at::MemoryFormat::ChannelsLast));
   at::Tensor bf;
-  const float* bp = nullptr;
-  if (bias.has_value()) {
-    bf = bias->to(at::kFloat).contiguous();
-    bp = bf.data_ptr<float>();
-  }
+  bool b_bf16 = false;
+  const void* bp = conv_bias_ptr(bias, bf, b_bf16);
   // split-K when the (pixels/128) x (K/128) grid starves the 256 CUs
   const int64_t NPQ = Nb * P * Q;
   int64_t blocks = ((NPQ + 127) / 128) * ((K + 127) / 128);
@@ -673,7 +733,7 @@ static at::Tensor conv2d_nhwc_fwd_v2_impl(at::Tensor x, at::Tensor w,
                 "conv temb: contiguous bf16 [N, K]");
     tp = temb->data_ptr();
   }
-  conv_nhwc_fwd_v2_launch(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), wsp,
+  conv_nhwc_fwd_v2_launch(x.data_ptr(), w.data_ptr(), bp, b_bf16, y.data_ptr(), wsp,
          splitz, rp, tp, (int)Nb, (int)Hin, (int)Win, (int)C, (int)K,
          (int)P, (int)Q, (int)R, (int)S, (int)stride,
          (int)pad, cur_stream());
@@ -793,7 +853,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("groupnorm_silu_nhwc_fwd", &groupnorm_silu_nhwc_fwd);
   mod.def("groupnorm_silu_nhwc_bwd", &groupnorm_silu_nhwc_bwd);
   mod.def("layernorm_fwd", &layernorm_fwd);
-  mod.def("layernorm_bwd", &layernorm_bwd);
+  mod.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"),
+          py::arg("w"), py::arg("mean"), py::arg("rstd"),
+          py::arg("blocks") = 0);
+  mod.def("colsum", &colsum);
+  mod.def("colsum_grouped", &colsum_grouped);
   mod.def("geglu_fwd", &geglu_fwd);
   mod.def("geglu_bwd", &geglu_bwd);
   mod.def("adamw_step", &adamw_step);

@@ -28,12 +28,21 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 using bf16_t = __hip_bfloat16;
 
+// bias arrives in the parameter's own dtype (bf16 or fp32) and is widened
+// here; bf16 -> fp32 is exact, so no cast kernel is needed in front.
+__device__ __forceinline__ float bias_at(const void* __restrict__ bias,
+                                         int bias_bf16, long k) {
+  if (!bias) return 0.f;
+  return bias_bf16 ? __bfloat162float(((const bf16_t*)bias)[k])
+                   : ((const float*)bias)[k];
+}
+
 #define CPITCH 40  // LDS row pitch (bf16) for the 32-wide A tile: 10 dwords
                    // -> 16-lane ds_read_b128 groups land on 16 distinct banks
 
 __global__ __launch_bounds__(256)
 void conv_nhwc_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                          const float* __restrict__ bias, bf16_t* __restrict__ y,
+                          const void* __restrict__ bias, int bias_bf16, bf16_t* __restrict__ y,
                           int Nb, int Hin, int Win, int C, int K, int P, int Q,
                           int R, int S, int stride, int pad) {
   __shared__ short sA[64 * CPITCH];
@@ -106,7 +115,7 @@ void conv_nhwc_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict
 #pragma unroll
     for (int ns = 0; ns < 4; ++ns) {
       const int k = k0 + ns * 16 + l16;
-      float v = acc[ns][rr] + (bias ? bias[k] : 0.f);
+      float v = acc[ns][rr] + bias_at(bias, bias_bf16, k);
       y[m * K + k] = __float2bfloat16(v);
     }
   }
@@ -118,16 +127,16 @@ void conv_nhwc_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict
 
 namespace dcr {
 
-void conv_nhwc_fwd_launch(const void* x, const void* w, const float* bias,
-                          void* y, int Nb, int Hin, int Win, int C, int K,
+void conv_nhwc_fwd_launch(const void* x, const void* w, const void* bias,
+                          bool bias_bf16, void* y, int Nb, int Hin, int Win, int C, int K,
                           int P, int Q, int R, int S, int stride, int pad,
                           hipStream_t st) {
   long NPQ = (long)Nb * P * Q;
   dim3 grid((unsigned)((NPQ + 63) / 64), (unsigned)(K / 64)), block(256);
   hipLaunchKernelGGL(dcr_conv::conv_nhwc_fwd_kernel, grid, block, 0, st,
                      (const dcr_conv::bf16_t*)x, (const dcr_conv::bf16_t*)w,
-                     bias, (dcr_conv::bf16_t*)y, Nb, Hin, Win, C, K, P, Q, R,
-                     S, stride, pad);
+                     bias, (int)bias_bf16, (dcr_conv::bf16_t*)y, Nb, Hin, Win, C,
+                     K, P, Q, R, S, stride, pad);
 }
 
 }  // namespace dcr
@@ -150,7 +159,7 @@ namespace dcr_conv {
 template <int BK>
 __global__ __launch_bounds__(256)
 void conv_nhwc_fwd_v2_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                             const float* __restrict__ bias, bf16_t* __restrict__ y,
+                             const void* __restrict__ bias, int bias_bf16, bf16_t* __restrict__ y,
                              float* __restrict__ ws, int splitz,
                              const bf16_t* __restrict__ res,
                              const bf16_t* __restrict__ temb,
@@ -268,7 +277,7 @@ void conv_nhwc_fwd_v2_kernel(const bf16_t* __restrict__ x, const bf16_t* __restr
         if (splitz > 1) {
           atomicAdd(&ws[m * K + k], acc[i][j][rr]);
         } else {
-          float v = acc[i][j][rr] + (bias ? bias[k] : 0.f);
+          float v = acc[i][j][rr] + bias_at(bias, bias_bf16, k);
           if (res) v += __bfloat162float(res[m * K + k]);
           if (temb) v += __bfloat162float(temb[(m / PQ) * K + k]);
           y[m * K + k] = __float2bfloat16(v);
@@ -279,14 +288,15 @@ void conv_nhwc_fwd_v2_kernel(const bf16_t* __restrict__ x, const bf16_t* __restr
 }
 
 __global__ void conv_splitk_finalize_kernel(const float* __restrict__ ws,
-                                            const float* __restrict__ bias,
+                                            const void* __restrict__ bias,
+                                            int bias_bf16,
                                             const bf16_t* __restrict__ res,
                                             const bf16_t* __restrict__ temb,
                                             bf16_t* __restrict__ y, long total,
                                             int K, int PQ) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long)gridDim.x * blockDim.x) {
-    float v = ws[i] + (bias ? bias[i % K] : 0.f);
+    float v = ws[i] + bias_at(bias, bias_bf16, i % K);
     if (res) v += __bfloat162float(res[i]);
     if (temb) v += __bfloat162float(temb[(i / ((long)K * PQ)) * K + i % K]);
     y[i] = __float2bfloat16(v);
@@ -297,8 +307,8 @@ __global__ void conv_splitk_finalize_kernel(const float* __restrict__ ws,
 
 namespace dcr {
 
-void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const float* bias,
-                             void* y, float* ws, int splitz, const void* res,
+void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const void* bias,
+                             bool bias_bf16, void* y, float* ws, int splitz, const void* res,
                              const void* temb, int Nb, int Hin, int Win, int C,
                              int K, int P, int Q, int R, int S, int stride,
                              int pad, hipStream_t st) {
@@ -311,13 +321,15 @@ void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const float* bias,
   if (C % 64 == 0)
     hipLaunchKernelGGL((dcr_conv::conv_nhwc_fwd_v2_kernel<64>), grid, block, 0,
                        st, (const dcr_conv::bf16_t*)x,
-                       (const dcr_conv::bf16_t*)w, bias, (dcr_conv::bf16_t*)y,
+                       (const dcr_conv::bf16_t*)w, bias, (int)bias_bf16,
+                       (dcr_conv::bf16_t*)y,
                        ws, splitz, rp, tp, Nb, Hin, Win, C, K, P, Q, R, S,
                        stride, pad);
   else
     hipLaunchKernelGGL((dcr_conv::conv_nhwc_fwd_v2_kernel<32>), grid, block, 0,
                        st, (const dcr_conv::bf16_t*)x,
-                       (const dcr_conv::bf16_t*)w, bias, (dcr_conv::bf16_t*)y,
+                       (const dcr_conv::bf16_t*)w, bias, (int)bias_bf16,
+                       (dcr_conv::bf16_t*)y,
                        ws, splitz, rp, tp, Nb, Hin, Win, C, K, P, Q, R, S,
                        stride, pad);
   if (splitz > 1) {
@@ -325,7 +337,8 @@ void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const float* bias,
     long b = (total / 4 + 255) / 256;
     if (b > 8192) b = 8192;
     hipLaunchKernelGGL(dcr_conv::conv_splitk_finalize_kernel,
-                       dim3((unsigned)b), dim3(256), 0, st, ws, bias, rp, tp,
+                       dim3((unsigned)b), dim3(256), 0, st, ws, bias,
+                       (int)bias_bf16, rp, tp,
                        (dcr_conv::bf16_t*)y, total, K, P * Q);
   }
 }

@@ -23,11 +23,20 @@ void ln_fwd_launch(DType dt, const void* x, const void* w, const void* b,
 void ln_bwd_launch(DType dt, const void* dy, const void* x, const void* w,
                    bool w_f32, const float* mean, const float* rstd, void* dx,
                    float* dw, float* db, long M, int N, hipStream_t s);
+// LN backward v2 (N <= 2048, N % 4 == 0): ln_bwd_v2_blocks() is the grid,
+// or 0 when the shape needs ln_bwd_launch (zeroed fp32 dw/db, atomics).
+// slab: blocks*2N floats, uninitialised; dwdb: [2N] in the weight dtype.
+int ln_bwd_v2_blocks(long M, int N);
+void ln_bwd_v2_launch(DType dt, const void* dy, const void* x, const void* w,
+                      bool w_f32, const float* mean, const float* rstd,
+                      void* dx, float* slab, void* dwdb, int blocks, long M,
+                      int N, hipStream_t s);
 
 // norms_nhwc.hip (channels_last GroupNorm; w_f32 as above).
 // Workspaces are per-chunk partial slabs (plain stores, deterministic,
 // no zero-init needed): fwd ws = chunks*N*G*2 floats; bwd ws =
 // chunks*N*G*2 + chunks*N*2C + N*G*2 floats. chunks = gn_nhwc_chunks().
+// bwd writes dw|db as one [2C] array in the weight dtype (dwdb).
 int gn_nhwc_chunks(int N, int R);
 void gn_nhwc_fwd_launch(DType dt, const void* x, const void* w, const void* b,
                         bool w_f32, void* y, float* ws, float* mean, float* rstd,
@@ -35,9 +44,18 @@ void gn_nhwc_fwd_launch(DType dt, const void* x, const void* w, const void* b,
                         hipStream_t s);
 void gn_nhwc_bwd_launch(DType dt, const void* dy, const void* x, const void* w,
                         const void* b, bool w_f32, const float* mean,
-                        const float* rstd, float* ws, void* dx, float* dw,
-                        float* db, int N, int R, int C, int G, bool silu,
+                        const float* rstd, float* ws, void* dx, void* dwdb,
+                        int N, int R, int C, int G, bool silu,
                         hipStream_t s);
+
+// reduce.hip — bias-gradient column sums of x [groups, rows_per_group, C].
+// chunks = colsum_chunks(dt, groups, rows_per_group, C, cap); slab holds
+// groups*chunks*C floats, uninitialised (unused when out_n is null and
+// chunks == 1: one launch). out_n [groups, C] may be null (groups == 1).
+int colsum_chunks(int dt, long groups, long rows_per_group, int C, int cap);
+void colsum_launch(DType dt, const void* x, float* slab, void* out_n, void* out,
+                   long groups, long rows_per_group, int C, int chunks,
+                   hipStream_t s);
 
 // elementwise.hip
 void geglu_fwd_launch(DType dt, const void* x, void* y, long M, long N,
@@ -109,13 +127,14 @@ void attn_bwd_v4_launch(const void* q, const void* k, const void* v,
                         hipStream_t s);
 void mfma_probe_launch(const void* A, const void* B, float* C, hipStream_t s);
 
-// conv_nhwc.hip (implicit-GEMM conv fwd, opt-in)
-void conv_nhwc_fwd_launch(const void* x, const void* w, const float* bias,
-                          void* y, int Nb, int Hin, int Win, int C, int K,
+// conv_nhwc.hip (implicit-GEMM conv fwd, opt-in); bias is fp32, or bf16
+// when bias_bf16 (widened in the epilogue)
+void conv_nhwc_fwd_launch(const void* x, const void* w, const void* bias,
+                          bool bias_bf16, void* y, int Nb, int Hin, int Win, int C, int K,
                           int P, int Q, int R, int S, int stride, int pad,
                           hipStream_t st);
-void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const float* bias,
-                             void* y, float* ws, int splitz, const void* res,
+void conv_nhwc_fwd_v2_launch(const void* x, const void* w, const void* bias,
+                             bool bias_bf16, void* y, float* ws, int splitz, const void* res,
                              const void* temb, int Nb, int Hin, int Win, int C,
                              int K, int P, int Q, int R, int S, int stride,
                              int pad, hipStream_t st);

@@ -12,6 +12,7 @@
 // * LayerNorm: one wave per row, 4 waves per block.
 
 #include "dcr_common.h"
+#include "dcr_reduce.h"
 
 using namespace dcr;
 
@@ -326,15 +327,178 @@ DCR_INST_T(__hip_bfloat16, __hip_bfloat16)
 DCR_INST_T(__half, float)
 DCR_INST_T(__half, __half)
 
-// forward decl (definition at end of file)
-template <typename T, typename WT>
-__global__ void ln_bwd_v2_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                 const WT* __restrict__ w,
-                                 const float* __restrict__ mean,
-                                 const float* __restrict__ rstd,
-                                 T* __restrict__ dx, float* __restrict__ dw,
-                                 float* __restrict__ db, long M, int N,
-                                 int rows_per_wave);
+// ===========================================================================
+// LayerNorm backward v2 (N <= 2048, N % 4 == 0): one wave per row with the
+// row resident in registers (loaded once for both the reduction and dx).
+// Shaped for bandwidth:
+// * NC (256-column chunks per row) is a template parameter, so N=320 costs
+//   2 chunks of registers and not 8: ~3x the waves per SIMD of a fixed
+//   8-chunk kernel.
+// * a wave walks rows row, row + waves_in_grid, ... and issues the loads of
+//   its next row before the current row's wave reduction, so two rows of
+//   x/dy per wave are in flight.
+// * dw/db accumulate in registers across the wave's rows, the block's
+//   waves are added in wave order through LDS, and the block writes one
+//   plain [2N] fp32 row of a [blocks, 2N] slab; slab_colsum_kernel adds
+//   the rows and writes dw|db in the weight dtype. No zero-init, no
+//   atomics, bit-reproducible.
+// The per-row arithmetic (element -> lane mapping, summation order, wave
+// butterfly) is unchanged from the first v2 kernel, so dx keeps its bits.
+// ===========================================================================
+#define LNB2_WAVES 8
+
+template <typename T> struct ln_raw4 { typedef uint2 type; };
+template <> struct ln_raw4<float> { typedef float4 type; };
+
+template <typename T>
+__device__ __forceinline__ typename ln_raw4<T>::type ln_load_raw(const T* __restrict__ p) {
+  return *reinterpret_cast<const typename ln_raw4<T>::type*>(p);
+}
+
+template <typename T>
+__device__ __forceinline__ f32x4 ln_unpack(typename ln_raw4<T>::type r) {
+  if constexpr (sizeof(T) == 4) {
+    return {r.x, r.y, r.z, r.w};
+  } else {
+    const T* e = reinterpret_cast<const T*>(&r);
+    return {to_f32<T>(e[0]), to_f32<T>(e[1]), to_f32<T>(e[2]), to_f32<T>(e[3])};
+  }
+}
+
+template <typename T, typename WT, int NC>
+__global__ __launch_bounds__(LNB2_WAVES * DCR_WAVE)
+void ln_bwd_v2_kernel(const T* __restrict__ dy, const T* __restrict__ x,
+                      const WT* __restrict__ w,
+                      const float* __restrict__ mean, const float* __restrict__ rstd,
+                      T* __restrict__ dx, float* __restrict__ slab, long M, int N) {
+  typedef typename ln_raw4<T>::type raw_t;
+  extern __shared__ float smem[];  // [2N]: dw | db of this block
+
+  const int wid = threadIdx.x / DCR_WAVE;
+  const int lane = threadIdx.x % DCR_WAVE;
+
+  float wv[NC][4], dwacc[NC][4], dbacc[NC][4];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int j = (c * DCR_WAVE + lane) * 4;
+    f32x4 ww = {0.f, 0.f, 0.f, 0.f};
+    if (j < N) ww = load4<WT>(w + j);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      wv[c][k] = (&ww.x)[k];
+      dwacc[c][k] = 0.f;
+      dbacc[c][k] = 0.f;
+    }
+  }
+
+  const long rstride = (long)gridDim.x * LNB2_WAVES;
+  long row = (long)blockIdx.x * LNB2_WAVES + wid;
+
+  raw_t xr[NC], gr[NC];
+  float m = 0.f, rs = 0.f;
+  if (row < M) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int j = (c * DCR_WAVE + lane) * 4;
+      if (j < N) {
+        xr[c] = ln_load_raw<T>(x + row * N + j);
+        gr[c] = ln_load_raw<T>(dy + row * N + j);
+      }
+    }
+    m = mean[row];
+    rs = rstd[row];
+  }
+
+  while (row < M) {
+    // next row's loads go out before this row's reduction
+    const long nrow = row + rstride;
+    raw_t nxr[NC], ngr[NC];
+    float nm = 0.f, nrs = 0.f;
+    if (nrow < M) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int j = (c * DCR_WAVE + lane) * 4;
+        if (j < N) {
+          nxr[c] = ln_load_raw<T>(x + nrow * N + j);
+          ngr[c] = ln_load_raw<T>(dy + nrow * N + j);
+        }
+      }
+      nm = mean[nrow];
+      nrs = rstd[nrow];
+    }
+
+    float xv[NC][4], gv[NC][4];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int j = (c * DCR_WAVE + lane) * 4;
+      if (j < N) {
+        f32x4 xx = ln_unpack<T>(xr[c]);
+        f32x4 gg = ln_unpack<T>(gr[c]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          xv[c][k] = (&xx.x)[k];
+          gv[c][k] = (&gg.x)[k];
+          float yh = (xv[c][k] - m) * rs;
+          float gw = gv[c][k] * wv[c][k];
+          s1 += gw;
+          s2 += gw * yh;
+          dwacc[c][k] += gv[c][k] * yh;
+          dbacc[c][k] += gv[c][k];
+        }
+      }
+    }
+    float2 s = wave_reduce_sum2(s1, s2);
+    const float m1 = s.x / N;
+    const float m2 = s.y / N;
+    T* dr = dx + row * N;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int j = (c * DCR_WAVE + lane) * 4;
+      if (j < N) {
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float yh = (xv[c][k] - m) * rs;
+          float gw = gv[c][k] * wv[c][k];
+          (&o.x)[k] = rs * (gw - m1 - yh * m2);
+        }
+        store4<T>(dr + j, o);
+      }
+    }
+
+    row = nrow;
+    m = nm;
+    rs = nrs;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { xr[c] = nxr[c]; gr[c] = ngr[c]; }
+  }
+
+  // block combine, wave 0 first then 1, 2, ... (fixed order)
+  for (int turn = 0; turn < LNB2_WAVES; ++turn) {
+    if (wid == turn) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int j = (c * DCR_WAVE + lane) * 4;
+        if (j < N) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (turn == 0) {
+              smem[j + k] = dwacc[c][k];
+              smem[N + j + k] = dbacc[c][k];
+            } else {
+              smem[j + k] += dwacc[c][k];
+              smem[N + j + k] += dbacc[c][k];
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  float* srow = slab + (long)blockIdx.x * 2 * N;
+  for (int j = threadIdx.x; j < 2 * N; j += blockDim.x) srow[j] = smem[j];
+}
 
 // ===========================================================================
 // Host launchers
@@ -434,22 +598,8 @@ template <typename T, typename WT>
 static void ln_bwd_t(const void* dy, const void* x, const void* w,
                      const float* mean, const float* rstd, void* dx, float* dw,
                      float* db, long M, int N, hipStream_t s) {
+  // v1: zero-initialised dw/db, LDS + global atomics (N > 2048 or N % 4)
   size_t lds = 2 * (size_t)N * sizeof(float);
-  if (N <= 2048 && (N & 3) == 0) {
-    // v2: register-resident rows, block handles 4 waves x rows_per_wave
-    const int waves = 4;
-    int rows_per_wave = 8;
-    long blocks = (M + (long)waves * rows_per_wave - 1) / ((long)waves * rows_per_wave);
-    if (blocks < 512 && M >= 512) {        // keep >= 512 WGs for 256 CUs
-      rows_per_wave = 1;
-      blocks = (M + waves - 1) / waves;
-    }
-    dim3 grid((unsigned)blocks), block(waves * DCR_WAVE);
-    hipLaunchKernelGGL((ln_bwd_v2_kernel<T, WT>), grid, block, lds, s, (const T*)dy,
-                       (const T*)x, (const WT*)w, mean, rstd, (T*)dx, dw, db, M, N,
-                       rows_per_wave);
-    return;
-  }
   const int waves = 4;
   dim3 grid((M + waves - 1) / waves), block(waves * DCR_WAVE);
   hipLaunchKernelGGL((ln_bwd_kernel<T, WT>), grid, block, lds, s, (const T*)dy,
@@ -472,122 +622,56 @@ void ln_bwd_launch(DType dt, const void* dy, const void* x, const void* w,
   }
 }
 
-}  // namespace dcr
+// v2 grid: 8-wave blocks, 2 rows per wave until 512 blocks, then more rows
+// per wave. The slab costs blocks * 2N * 4 B written and read once; at
+// 512 blocks that is 8 % of the x/dy/dx traffic at 16384x320 and the
+// grid still puts 4 waves on every SIMD.
+int ln_bwd_v2_blocks(long M, int N) {
+  if (N > 2048 || (N & 3) != 0) return 0;
+  long blocks = (M + 2 * LNB2_WAVES - 1) / (2 * LNB2_WAVES);
+  if (blocks > 512) blocks = 512;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
 
-// ===========================================================================
-// LayerNorm backward v2 (N <= 2048, N % 4 == 0): one wave per row, rows
-// processed sequentially per wave with the row RESIDENT IN REGISTERS
-// (load once for both the reduction and dx), dw/db accumulated in
-// registers across the wave's rows and flushed once per block.
-// Replaces per-element LDS atomics (profiles/prof4: ln_bwd 3.4 ms/step).
-// ===========================================================================
-#define LNB2_MAXCHUNK 8  // N <= 8*256 = 2048
+template <typename T, typename WT, int NC>
+static void ln_bwd_v2_nc(const void* dy, const void* x, const void* w,
+                         const float* mean, const float* rstd, void* dx,
+                         float* slab, int blocks, long M, int N, hipStream_t s) {
+  size_t lds = 2 * (size_t)N * sizeof(float);
+  hipLaunchKernelGGL((ln_bwd_v2_kernel<T, WT, NC>), dim3((unsigned)blocks),
+                     dim3(LNB2_WAVES * DCR_WAVE), lds, s, (const T*)dy,
+                     (const T*)x, (const WT*)w, mean, rstd, (T*)dx, slab, M, N);
+}
 
 template <typename T, typename WT>
-__global__ __launch_bounds__(256)
-void ln_bwd_v2_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                      const WT* __restrict__ w,
-                      const float* __restrict__ mean, const float* __restrict__ rstd,
-                      T* __restrict__ dx, float* __restrict__ dw,
-                      float* __restrict__ db, long M, int N, int rows_per_wave) {
-  extern __shared__ float smem[];  // [2N]
-  float* dw_l = smem;
-  float* db_l = smem + N;
-  for (int j = threadIdx.x; j < 2 * N; j += blockDim.x) smem[j] = 0.f;
-
-  const int wid = threadIdx.x / DCR_WAVE;
-  const int lane = threadIdx.x % DCR_WAVE;
+static void ln_bwd_v2_t(const void* dy, const void* x, const void* w,
+                        const float* mean, const float* rstd, void* dx,
+                        float* slab, void* dwdb, int blocks, long M, int N,
+                        hipStream_t s) {
   const int nchunk = (N + DCR_WAVE * 4 - 1) / (DCR_WAVE * 4);
+  if (nchunk <= 2) ln_bwd_v2_nc<T, WT, 2>(dy, x, w, mean, rstd, dx, slab, blocks, M, N, s);
+  else if (nchunk <= 3) ln_bwd_v2_nc<T, WT, 3>(dy, x, w, mean, rstd, dx, slab, blocks, M, N, s);
+  else if (nchunk <= 5) ln_bwd_v2_nc<T, WT, 5>(dy, x, w, mean, rstd, dx, slab, blocks, M, N, s);
+  else ln_bwd_v2_nc<T, WT, 8>(dy, x, w, mean, rstd, dx, slab, blocks, M, N, s);
+  slab_colsum_launch<WT>(slab, dwdb, blocks, 2 * N, 2L * N, s);
+}
 
-  float dwacc[LNB2_MAXCHUNK][4];
-  float dbacc[LNB2_MAXCHUNK][4];
-#pragma unroll
-  for (int c = 0; c < LNB2_MAXCHUNK; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { dwacc[c][k] = 0.f; dbacc[c][k] = 0.f; }
-
-  const long row0 = ((long)blockIdx.x * (blockDim.x / DCR_WAVE) + wid) * rows_per_wave;
-  for (long row = row0; row < min(row0 + rows_per_wave, M); ++row) {
-    const T* xr = x + row * N;
-    const T* gr = dy + row * N;
-    T* dr = dx + row * N;
-    const float m = mean[row];
-    const float rs = rstd[row];
-
-    float xv[LNB2_MAXCHUNK][4], gv[LNB2_MAXCHUNK][4], wv[LNB2_MAXCHUNK][4];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < LNB2_MAXCHUNK; ++c) {
-      int j = (c * DCR_WAVE + lane) * 4;
-      if (c < nchunk && j < N) {
-        f32x4 xx = load4<T>(xr + j);
-        f32x4 gg = load4<T>(gr + j);
-        f32x4 ww = load4<WT>(w + j);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          xv[c][k] = (&xx.x)[k];
-          gv[c][k] = (&gg.x)[k];
-          wv[c][k] = (&ww.x)[k];
-          float yh = (xv[c][k] - m) * rs;
-          float gw = gv[c][k] * wv[c][k];
-          s1 += gw;
-          s2 += gw * yh;
-          dwacc[c][k] += gv[c][k] * yh;
-          dbacc[c][k] += gv[c][k];
-        }
-      }
-    }
-    float2 s = wave_reduce_sum2(s1, s2);
-    const float m1 = s.x / N;
-    const float m2 = s.y / N;
-#pragma unroll
-    for (int c = 0; c < LNB2_MAXCHUNK; ++c) {
-      int j = (c * DCR_WAVE + lane) * 4;
-      if (c < nchunk && j < N) {
-        f32x4 o;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float yh = (xv[c][k] - m) * rs;
-          float gw = gv[c][k] * wv[c][k];
-          (&o.x)[k] = rs * (gw - m1 - yh * m2);
-        }
-        store4<T>(dr + j, o);
-      }
-    }
-  }
-
-  __syncthreads();  // LDS zero-init visible
-#pragma unroll
-  for (int c = 0; c < LNB2_MAXCHUNK; ++c) {
-    int j = (c * DCR_WAVE + lane) * 4;
-    if (c < nchunk && j < N) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        atomicAdd(&dw_l[j + k], dwacc[c][k]);   // 4-way (one per wave)
-        atomicAdd(&db_l[j + k], dbacc[c][k]);
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < N; j += blockDim.x) {
-    atomicAdd(&dw[j], dw_l[j]);
-    atomicAdd(&db[j], db_l[j]);
+void ln_bwd_v2_launch(DType dt, const void* dy, const void* x, const void* w,
+                      bool w_f32, const float* mean, const float* rstd,
+                      void* dx, float* slab, void* dwdb, int blocks, long M,
+                      int N, hipStream_t s) {
+  switch (dt) {
+    case DT_F32: ln_bwd_v2_t<float, float>(dy, x, w, mean, rstd, dx, slab, dwdb, blocks, M, N, s); break;
+    case DT_F16:
+      if (w_f32) ln_bwd_v2_t<__half, float>(dy, x, w, mean, rstd, dx, slab, dwdb, blocks, M, N, s);
+      else ln_bwd_v2_t<__half, __half>(dy, x, w, mean, rstd, dx, slab, dwdb, blocks, M, N, s);
+      break;
+    case DT_BF16:
+      if (w_f32) ln_bwd_v2_t<__hip_bfloat16, float>(dy, x, w, mean, rstd, dx, slab, dwdb, blocks, M, N, s);
+      else ln_bwd_v2_t<__hip_bfloat16, __hip_bfloat16>(dy, x, w, mean, rstd, dx, slab, dwdb, blocks, M, N, s);
+      break;
   }
 }
 
-namespace dcr {
-
-void ln_bwd_v2_wire() {}  // anchor
-
 }  // namespace dcr
-
-#define DCR_INST_LNB2(T, WT)                                                   \
-  template __global__ void ln_bwd_v2_kernel<T, WT>(const T*, const T*,         \
-      const WT*, const float*, const float*, T*, float*, float*, long,         \
-      int, int);
-
-DCR_INST_LNB2(float, float)
-DCR_INST_LNB2(__hip_bfloat16, float)
-DCR_INST_LNB2(__hip_bfloat16, __hip_bfloat16)
-DCR_INST_LNB2(__half, float)
-DCR_INST_LNB2(__half, __half)

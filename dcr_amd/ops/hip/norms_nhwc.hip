@@ -17,6 +17,7 @@
 // G13) whenever C % 8 == 0 (every SD-2.1/VAE channel count), else 4.
 
 #include "dcr_common.h"
+#include "dcr_reduce.h"
 
 using namespace dcr;
 
@@ -134,9 +135,19 @@ __global__ void gn_finalize_kernel(const float* __restrict__ ws,
 
 // reduce the bwd partial slabs: group sums [chunks, N, G, 2] -> [N*G, 2]
 // and per-channel dw/db [chunks*N, 2C] -> dw[C], db[C]
-__global__ void gn_bwd_finalize_groups_kernel(const float* __restrict__ ws,
-                                              float* __restrict__ out, long NG,
-                                              int chunks) {
+// One launch: the first `gblocks` blocks add the group sums over chunks in
+// chunk order (what dx is built from), the rest add the dw|db slab rows
+// and write them in the weight dtype.
+template <typename WT>
+__global__ __launch_bounds__(256)
+void gn_bwd_finalize_kernel(const float* __restrict__ ws, float* __restrict__ out,
+                            long NG, int chunks, int gblocks,
+                            const float* __restrict__ slab, WT* __restrict__ dwdb,
+                            int C2, long rows) {
+  if ((int)blockIdx.x >= gblocks) {
+    slab_colsum_block<WT>(slab, dwdb, rows, C2, (long)C2, (int)blockIdx.x - gblocks);
+    return;
+  }
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= NG) return;
   float s1 = 0.f, s2 = 0.f;
@@ -146,21 +157,6 @@ __global__ void gn_bwd_finalize_groups_kernel(const float* __restrict__ ws,
   }
   out[i * 2] = s1;
   out[i * 2 + 1] = s2;
-}
-
-__global__ void gn_bwd_finalize_dwdb_kernel(const float* __restrict__ slab,
-                                            float* __restrict__ dw,
-                                            float* __restrict__ db, int C,
-                                            long rows) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  float a = 0.f, b = 0.f;
-  for (long r = 0; r < rows; ++r) {
-    a += slab[r * 2 * C + c];
-    b += slab[r * 2 * C + C + c];
-  }
-  dw[c] = a;
-  db[c] = b;
 }
 
 // --------------------------------------------------------------- apply fwd
@@ -204,8 +200,8 @@ __global__ void gn_nhwc_bwd_stats_kernel(const T* __restrict__ dy, const T* __re
                                          float* __restrict__ ws,
                                          float* __restrict__ dwdb_slab,
                                          int N, int R, int C, int G, int rows_per_blk) {
-  // smem [4*C]: per-channel S1/S2 (group sums) + per-channel dw/db
-  // partials; everything leaves the block as PLAIN per-chunk slab
+  // smem [4*C] (x row groups when narrow): per-channel S1/S2 (group
+  // sums) + per-channel dw/db partials; everything leaves the block as PLAIN per-chunk slab
   // stores (no global atomics at all — deterministic, no zero-init;
   // the per-channel-atomic version measured 3.5-4.6x slower at V=8
   // from contention; finalize kernels reduce the slabs).
@@ -226,8 +222,10 @@ __global__ void gn_nhwc_bwd_stats_kernel(const T* __restrict__ dy, const T* __re
   int tpr = wide ? (int)blockDim.x : C / V;
   int rpar = wide ? 1 : (int)blockDim.x / tpr;
   int rgrp = wide ? 0 : (int)threadIdx.x / tpr;
-  for (int c = threadIdx.x; c < 4 * C; c += blockDim.x) smem[c] = 0.f;
-  __syncthreads();
+  // narrow-C: row group rg fills its own [4C] row of smem (every slot is
+  // written, so nothing is zeroed); the rows are added in rg order below.
+  // LDS float atomics here made the sums depend on arrival order.
+  float* mine = smem + (long)(rgrp < rpar ? rgrp : 0) * 4 * C;
   for (int c0 = (wide ? (int)threadIdx.x * V : ((int)threadIdx.x % tpr) * V);
        c0 < C; c0 += (wide ? (int)blockDim.x * V : C + 1)) {
     if (rgrp >= rpar) break;
@@ -261,20 +259,21 @@ __global__ void gn_nhwc_bwd_stats_kernel(const T* __restrict__ dy, const T* __re
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      if (wide) {
-        sa[c0 + k] = a[k];
-        sb[c0 + k] = bb[k];
-        sdw[c0 + k] = dwc[k];
-        sdb[c0 + k] = dbc[k];
-      } else {
-        atomicAdd(&sa[c0 + k], a[k]);
-        atomicAdd(&sb[c0 + k], bb[k]);
-        atomicAdd(&sdw[c0 + k], dwc[k]);
-        atomicAdd(&sdb[c0 + k], dbc[k]);
-      }
+      mine[c0 + k] = a[k];
+      mine[C + c0 + k] = bb[k];
+      mine[2 * C + c0 + k] = dwc[k];
+      mine[3 * C + c0 + k] = dbc[k];
     }
   }
   __syncthreads();
+  if (rpar > 1) {
+    for (int i = threadIdx.x; i < 4 * C; i += blockDim.x) {
+      float acc = smem[i];
+      for (int rg = 1; rg < rpar; ++rg) acc += smem[(long)rg * 4 * C + i];
+      smem[i] = acc;
+    }
+    __syncthreads();
+  }
   float* drow = dwdb_slab + ((long)blockIdx.x * N + n) * 2 * C;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     drow[c] = sdw[c];
@@ -402,12 +401,14 @@ void gn_nhwc_fwd_launch(DType dt, const void* x, const void* w, const void* b,
 template <typename T, typename WT, int V>
 static void gn_nhwc_bwd_v(const void* dy, const void* x, const void* w,
                           const void* b, const float* mean, const float* rstd,
-                          float* ws, void* dx, float* dw, float* db, int N,
+                          float* ws, void* dx, void* dwdb, int N,
                           int R, int C, int G, bool silu, hipStream_t s) {
   int chunks = nhwc_row_chunks(N, R);
   int rows_per_blk = (R + chunks - 1) / chunks;
   dim3 grid(chunks, N), block(256);
-  size_t lds = 4 * (size_t)C * sizeof(float);
+  // narrow-C (C < 256*V) keeps one [4C] LDS row per row group: <= 32 KB
+  const int rpar = (C >= 256 * V) ? 1 : 256 / (C / V);
+  size_t lds = 4 * (size_t)C * rpar * sizeof(float);
   // slab layout: ws_slab [chunks, N, G, 2] | dwdb_slab [chunks*N, 2C] |
   // finalized groups [N*G, 2] (the pointers are carved by the binding)
   long NG = (long)N * G;
@@ -422,12 +423,12 @@ static void gn_nhwc_bwd_v(const void* dy, const void* x, const void* w,
     hipLaunchKernelGGL((dcr_nhwc::gn_nhwc_bwd_stats_kernel<T, WT, false, V>), grid, block, lds, s,
                        (const T*)dy, (const T*)x, (const WT*)w, (const WT*)b, mean, rstd,
                        ws_slab, dwdb_slab, N, R, C, G, rows_per_blk);
-  hipLaunchKernelGGL(dcr_nhwc::gn_bwd_finalize_groups_kernel,
-                     dim3((NG + 255) / 256), dim3(256), 0, s, ws_slab, ws_fin,
-                     NG, chunks);
-  hipLaunchKernelGGL(dcr_nhwc::gn_bwd_finalize_dwdb_kernel,
-                     dim3((C + 255) / 256), dim3(256), 0, s, dwdb_slab, dw, db,
-                     C, (long)chunks * N);
+  const int gblocks = (int)((NG + 255) / 256);
+  const int cblocks = (2 * C + DCR_SLAB_COLS - 1) / DCR_SLAB_COLS;
+  hipLaunchKernelGGL((dcr_nhwc::gn_bwd_finalize_kernel<WT>),
+                     dim3(gblocks + cblocks), dim3(256), 0, s, ws_slab, ws_fin,
+                     NG, chunks, gblocks, dwdb_slab, (WT*)dwdb, 2 * C,
+                     (long)chunks * N);
   long total = (long)N * R * C;
   float inv_L = 1.f / ((float)R * (C / G));
   dim3 agrid((int)min((total / V + 255) / 256, (long)8192)), ablock(256);
@@ -444,28 +445,28 @@ static void gn_nhwc_bwd_v(const void* dy, const void* x, const void* w,
 template <typename T, typename WT>
 static void gn_nhwc_bwd_t(const void* dy, const void* x, const void* w,
                           const void* b, const float* mean, const float* rstd,
-                          float* ws, void* dx, float* dw, float* db, int N,
+                          float* ws, void* dx, void* dwdb, int N,
                           int R, int C, int G, bool silu, hipStream_t s) {
   if (C % 8 == 0 && sizeof(T) == 2)
-    gn_nhwc_bwd_v<T, WT, 8>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
+    gn_nhwc_bwd_v<T, WT, 8>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
   else
-    gn_nhwc_bwd_v<T, WT, 4>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
+    gn_nhwc_bwd_v<T, WT, 4>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
 }
 
 void gn_nhwc_bwd_launch(DType dt, const void* dy, const void* x, const void* w,
                         const void* b, bool w_f32, const float* mean,
-                        const float* rstd, float* ws, void* dx, float* dw,
-                        float* db, int N, int R, int C, int G, bool silu,
+                        const float* rstd, float* ws, void* dx, void* dwdb,
+                        int N, int R, int C, int G, bool silu,
                         hipStream_t s) {
   switch (dt) {
-    case DT_F32: gn_nhwc_bwd_t<float, float>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s); break;
+    case DT_F32: gn_nhwc_bwd_t<float, float>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s); break;
     case DT_F16:
-      if (w_f32) gn_nhwc_bwd_t<__half, float>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
-      else gn_nhwc_bwd_t<__half, __half>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
+      if (w_f32) gn_nhwc_bwd_t<__half, float>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
+      else gn_nhwc_bwd_t<__half, __half>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
       break;
     case DT_BF16:
-      if (w_f32) gn_nhwc_bwd_t<__hip_bfloat16, float>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
-      else gn_nhwc_bwd_t<__hip_bfloat16, __hip_bfloat16>(dy, x, w, b, mean, rstd, ws, dx, dw, db, N, R, C, G, silu, s);
+      if (w_f32) gn_nhwc_bwd_t<__hip_bfloat16, float>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
+      else gn_nhwc_bwd_t<__hip_bfloat16, __hip_bfloat16>(dy, x, w, b, mean, rstd, ws, dx, dwdb, N, R, C, G, silu, s);
       break;
   }
 }

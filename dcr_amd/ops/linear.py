@@ -18,6 +18,10 @@ diffusers) through cuBLAS. Round-2 measurement on MI355X
 
 DCR_NATIVE_GEMM=1 enables the hybrid (native wgrad) path;
 DCR_NATIVE_GEMM=full forces all three passes native (benching only).
+
+On the default path the GEMMs stay with the library and only the bias
+gradient is native: reduce.hip's column sum replaces the aten reduction
+(_BiasGradLinear). DCR_NATIVE_BIAS_GRAD=0, read per call, turns that off.
 """
 from __future__ import annotations
 
@@ -39,7 +43,48 @@ def _wgrad_eligible(x2d: torch.Tensor, weight: torch.Tensor) -> bool:
     M, K = x2d.shape
     N = weight.shape[0]
     return (x2d.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-            and K % 8 == 0 and N % 8 == 0 and M >= 4096)
+            and K % 8 == 0 and N % 8 == 0 and M % 8 == 0 and M >= 4096)
+
+
+def _bias_grad_enabled() -> bool:
+    return os.environ.get("DCR_NATIVE_BIAS_GRAD", "1") != "0"
+
+
+# Below this many rows of dy the native column sum is not dispatched. The
+# only such linears in the UNet are the [16, C] time-embedding projections:
+# scripts/bench_norms.py measured 4.1 us native against 5.1 us aten at
+# 16x1280 (profiles/r06_bench_norms.log): 1 us per call, 26 calls a step,
+# less than the host time a Python autograd Function adds to each of them
+# in the eager step (reasoned, not measured in the model). From 256 rows up
+# the kernel measured 1.2-3.6x the aten reduction.
+_BIAS_GRAD_MIN_ROWS = 64
+
+
+class _BiasGradLinear(torch.autograd.Function):
+    """Default path: library GEMMs for all three passes, exactly the ones
+    autograd issues for F.linear (dy @ W, dy.T @ x), and the bias gradient
+    from the native column-sum kernel instead of an aten reduction."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        y = F.linear(x, weight, bias)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = (dy2 @ weight).view(x.shape)
+        if ctx.needs_input_grad[1]:
+            dw = dy2.t() @ x.reshape(-1, x.shape[-1])
+        if ctx.needs_input_grad[2]:
+            m = require_hip("colsum")
+            count_dispatch("bias_grad")
+            db = m.colsum(dy2.contiguous())
+        return dx, dw, db
 
 
 class _HybridLinear(torch.autograd.Function):
@@ -113,6 +158,13 @@ def dcr_linear(x: torch.Tensor, weight: torch.Tensor,
             fn = _FullNativeLinear if mode == "full" else _HybridLinear
             y = fn.apply(x2d.contiguous(), weight.contiguous(), bias)
             return y.reshape(*x.shape[:-1], weight.shape[0])
+    if bias is not None and bias.requires_grad and use_hip(x) \
+            and torch.is_grad_enabled() and _bias_grad_enabled() \
+            and not torch.is_autocast_enabled() \
+            and x.dtype == weight.dtype == bias.dtype \
+            and x.dtype in (torch.bfloat16, torch.float16, torch.float32) \
+            and x.numel() // x.shape[-1] >= _BIAS_GRAD_MIN_ROWS:
+        return _BiasGradLinear.apply(x, weight, bias)
     return F.linear(x, weight, bias)
 
 
