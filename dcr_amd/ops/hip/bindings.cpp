@@ -829,8 +829,43 @@ std::vector<at::Tensor> gemm_bf16(at::Tensor A, at::Tensor B,
   return {C};
 }
 
+// dw[N,K] = dy2d[M,N]^T x2d[M,K] (+ db[N] = column sums of dy2d), bf16 with
+// fp32 accumulation: one split-contraction MFMA launch into an fp32 slab and
+// one ordered slab reduction. split = 0 / tile = 0 take the launcher's rule.
+// dw and db are views of one [N*K (+N)] buffer.
+std::vector<at::Tensor> linear_wgrad(at::Tensor dy, at::Tensor x, bool want_db,
+                                     int64_t split, int64_t tile) {
+  TORCH_CHECK(dy.is_cuda() && x.is_cuda() &&
+              dy.scalar_type() == at::kBFloat16 &&
+              x.scalar_type() == at::kBFloat16, "linear_wgrad: bf16 CUDA only");
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && dy.is_contiguous() &&
+              x.is_contiguous(), "linear_wgrad: contiguous 2-D expected");
+  const int64_t M = dy.size(0), N = dy.size(1), K = x.size(1);
+  TORCH_CHECK(x.size(0) == M, "linear_wgrad: row mismatch");
+  TORCH_CHECK(M >= 1 && N % 8 == 0 && K % 8 == 0 && N >= 8 && K >= 8,
+              "linear_wgrad: N % 8 == 0 and K % 8 == 0 expected");
+  TORCH_CHECK(N * K + N < (1LL << 31) && split >= 0 && split < (1 << 16));
+  TORCH_CHECK(M * std::max(N, K) < (1LL << 30),
+              "linear_wgrad: operands of 2 GiB and more are not supported "
+              "(32-bit buffer offsets)");
+  int tn, sp, cps;
+  linear_wgrad_plan(M, (int)N, (int)K, (int)tile, (int)split, &tn, &sp, &cps);
+  const int64_t ld = N * K + (want_db ? N : 0);
+  auto slab = at::empty({sp * ld}, dy.options().dtype(at::kFloat));
+  auto out = at::empty({ld}, dy.options());
+  linear_wgrad_launch(dy.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                      out.data_ptr(), M, (int)N, (int)K, want_db ? 1 : 0, tn,
+                      sp, cps, cur_stream());
+  auto dw = out.narrow(0, 0, N * K).view({N, K});
+  if (want_db) return {dw, out.narrow(0, N * K, N)};
+  return {dw};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_bf16", &gemm_bf16);
+  mod.def("linear_wgrad", &linear_wgrad, pybind11::arg("dy2d"),
+          pybind11::arg("x2d"), pybind11::arg("want_db"),
+          pybind11::arg("split") = 0, pybind11::arg("tile") = 0);
   mod.def("conv2d_nhwc_bwd", &conv2d_nhwc_bwd);
   mod.def("conv2d_nhwc_fwd", &conv2d_nhwc_fwd);
   mod.def("conv2d_nhwc_fwd_v2", &conv2d_nhwc_fwd_v2,

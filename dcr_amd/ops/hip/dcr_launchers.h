@@ -154,5 +154,14 @@ void gemm_bf16_launch(const void* A, const void* B, const float* bias,
                       void* C, float* ws, float* dbias, long M, long N, int K,
                       int ta, int tb, int want_dbias, int splitz,
                       hipStream_t st);
+// split-contraction weight gradient dW = dy^T x (+ db = column sums of dy),
+// bf16. slab: split * (N*K + (want_db ? N : 0)) floats, uninitialised;
+// dwdb: N*K (+ N) bf16. tile/split/chunks_per_slice from linear_wgrad_plan.
+void linear_wgrad_plan(long M, int N, int K, int tile_req, int split_req,
+                       int* tile, int* split, int* chunks_per_slice);
+void linear_wgrad_launch(const void* dy, const void* x, float* slab,
+                         void* dwdb, long M, int N, int K, int want_db,
+                         int tile, int split, int chunks_per_slice,
+                         hipStream_t st);
 
 }  // namespace dcr

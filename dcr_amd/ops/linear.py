@@ -1,27 +1,40 @@
-"""Linear-layer dispatch: rocBLAS forward/dgrad + hand-written MFMA wgrad.
+"""Linear-layer dispatch: library forward/dgrad, native weight gradient
+where the library's starves the GPU, native bias gradient.
 
 The reference runs every UNet linear (QKV/out projections, GEGLU
-FeedForward matmuls, proj_in/out — /root/reference/diff_train.py:644 via
-diffusers) through cuBLAS. Round-2 measurement on MI355X
-(scripts/bench_gemm.py, gpurun_out/r02c2_bench_gemm.log):
+FeedForward matmuls, proj_in/out) through the vendor BLAS. Here:
 
-* fwd / dgrad: the in-tree 128x128 2-barrier MFMA kernel reaches
-  77-373 TF = 0.42-0.59x rocBLAS/Tensile on the SD-2.1 shapes — Tensile
-  keeps those passes.
-* wgrad + fused bias-grad measured 0.98-1.13x in the ISOLATED microbench
-  at contraction >= 4096, but the whole-model profile
-  (profiles/r02_prof_head.md) shows it costing 40 ms/6-steps vs the
-  ~25 ms of Tensile wgrad + aten bias-reduce it replaced — the
-  microbench's rocBLAS side was inflated by an fp32 cast in the
-  reference timing. Net in-model loss, so native linear dispatch is
-  DEFAULT OFF.
+* forward and dgrad stay with rocBLAS/Tensile: the in-tree 128x128 MFMA
+  kernel (`gemm_bf16`) reaches 0.42-0.59x of it on the SD-2.1 shapes
+  (scripts/bench_gemm.py).
+* the weight gradient dy.T @ x goes to `linear_wgrad` (gemm.hip: split
+  contraction, fp32 slab, ordered reduction, fused bias gradient) for the
+  shapes `_native_wgrad_rule(M, N, K)` accepts. The library runs one
+  workgroup per 64x64 tile of dW over all M rows, so the 320x320 layers
+  with 16384 rows occupy 25 of 256 CUs for 102 us; the native pair of
+  launches takes 19 us (scripts/bench_wgrad.py, operands rotated through a
+  pool larger than the last-level cache; table and sweep in
+  dcr_amd/ops/hip/README.md). Measured wins, native dw against dy.t() @ x
+  alone / native dw+db against library + colsum: 16384x320x320 5.6x / 6.0x,
+  16384x320x1280 3.2x / 3.3x, 16384x2560x320 1.16x / 1.35x, 4096x640x640
+  1.38x / 1.69x, 1232x320x1024 1.50x (bias-free). Measured losses, left
+  with the library: 4096x640x2560 0.72x, 4096x5120x640 0.44x, every
+  1024-row level-2 shape 0.18-0.61x, 1232x640x1024 0.89x, 1232x1280x1024
+  0.82x. In the model the step went from 68.0-68.3 to 63.2-63.4 ms
+  (profiles/r07_prof_*.md). DCR_NATIVE_WGRAD=0, read per call, restores
+  the library weight gradient exactly.
+* elsewhere the bias gradient alone is native: reduce.hip's column sum
+  replaces the aten reduction. DCR_NATIVE_BIAS_GRAD=0, read per call, turns
+  that off.
 
-DCR_NATIVE_GEMM=1 enables the hybrid (native wgrad) path;
-DCR_NATIVE_GEMM=full forces all three passes native (benching only).
+All of the above is one autograd Function, `_DefaultLinear`; bias-free
+linears reach it only for the native weight gradient.
 
-On the default path the GEMMs stay with the library and only the bias
-gradient is native: reduce.hip's column sum replaces the aten reduction
-(_BiasGradLinear). DCR_NATIVE_BIAS_GRAD=0, read per call, turns that off.
+The older `gemm_bf16(ta=1, tb=1)` weight gradient (two-byte transposed
+gathers, fp32 atomics into a zero-filled workspace + finalize) measured
+83 us at 16384x320x320 and lost in the whole-model profile
+(profiles/r02_prof_head.md); it stays behind DCR_NATIVE_GEMM=1 (hybrid)
+and DCR_NATIVE_GEMM=full (all three passes native, benching only).
 """
 from __future__ import annotations
 
@@ -60,15 +73,45 @@ def _bias_grad_enabled() -> bool:
 _BIAS_GRAD_MIN_ROWS = 64
 
 
-class _BiasGradLinear(torch.autograd.Function):
-    """Default path: library GEMMs for all three passes, exactly the ones
-    autograd issues for F.linear (dy @ W, dy.T @ x), and the bias gradient
-    from the native column-sum kernel instead of an aten reduction."""
+def _native_wgrad_enabled() -> bool:
+    return os.environ.get("DCR_NATIVE_WGRAD", "1") != "0"
+
+
+# linear_wgrad (gemm.hip) takes dw (+ db) where the library's weight
+# gradient starves the GPU: it runs one workgroup per 64x64 tile of dW, each
+# walking all M rows, so with fewer tiles than the 256 CUs its time is set
+# by M alone (about 6.7 ns a row: 108 us at 16384 rows, 28 us at 4096)
+# whatever N and K are. The native pair of launches costs about 14 us at
+# the least, and its time grows with the operand re-reads, that is with
+# the tile count. Measured with scripts/bench_wgrad.py (module docstring):
+# up to 100 tiles it wins from 1232 rows on; between 100 and 256 tiles only
+# the 16384-row GEGLU projection was measured to win, the 1232-row context
+# projection with 160 tiles was not; above 256 tiles the library wins.
+_WGRAD_SMALL_TILES, _WGRAD_SMALL_MIN_ROWS = 100, 1024
+_WGRAD_MAX_TILES, _WGRAD_MIN_ROWS = 256, 8192
+
+
+def _native_wgrad_rule(M: int, N: int, K: int) -> bool:
+    if N % 8 or K % 8 or M * max(N, K) >= 1 << 30:   # the kernel's limits
+        return False
+    tiles = ((N + 63) // 64) * ((K + 63) // 64)
+    if tiles <= _WGRAD_SMALL_TILES:
+        return M >= _WGRAD_SMALL_MIN_ROWS
+    return tiles <= _WGRAD_MAX_TILES and M >= _WGRAD_MIN_ROWS
+
+
+class _DefaultLinear(torch.autograd.Function):
+    """Default path: library GEMMs for forward and dgrad, exactly the ones
+    autograd issues for F.linear. With `native_wgrad`, dw and db come from
+    one linear_wgrad call (split-contraction MFMA kernel + ordered slab
+    reduction); otherwise dw is the library's dy.T @ x and the bias gradient
+    the native column-sum kernel instead of an aten reduction."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, native_wgrad):
         y = F.linear(x, weight, bias)
         ctx.save_for_backward(x, weight)
+        ctx.native_wgrad = native_wgrad
         return y
 
     @staticmethod
@@ -78,13 +121,23 @@ class _BiasGradLinear(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = (dy2 @ weight).view(x.shape)
+        if ctx.native_wgrad and ctx.needs_input_grad[1]:
+            m = require_hip("linear_wgrad")
+            count_dispatch("linear_wgrad")
+            out = m.linear_wgrad(dy2.contiguous(),
+                                 x.reshape(-1, x.shape[-1]).contiguous(),
+                                 bool(ctx.needs_input_grad[2]))
+            dw = out[0]
+            if ctx.needs_input_grad[2]:
+                db = out[1]
+            return dx, dw, db, None
         if ctx.needs_input_grad[1]:
             dw = dy2.t() @ x.reshape(-1, x.shape[-1])
         if ctx.needs_input_grad[2]:
             m = require_hip("colsum")
             count_dispatch("bias_grad")
             db = m.colsum(dy2.contiguous())
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 class _HybridLinear(torch.autograd.Function):
@@ -158,13 +211,19 @@ def dcr_linear(x: torch.Tensor, weight: torch.Tensor,
             fn = _FullNativeLinear if mode == "full" else _HybridLinear
             y = fn.apply(x2d.contiguous(), weight.contiguous(), bias)
             return y.reshape(*x.shape[:-1], weight.shape[0])
-    if bias is not None and bias.requires_grad and use_hip(x) \
-            and torch.is_grad_enabled() and _bias_grad_enabled() \
-            and not torch.is_autocast_enabled() \
-            and x.dtype == weight.dtype == bias.dtype \
-            and x.dtype in (torch.bfloat16, torch.float16, torch.float32) \
-            and x.numel() // x.shape[-1] >= _BIAS_GRAD_MIN_ROWS:
-        return _BiasGradLinear.apply(x, weight, bias)
+    if use_hip(x) and torch.is_grad_enabled() \
+            and not torch.is_autocast_enabled():
+        rows = x.numel() // x.shape[-1]
+        if weight.requires_grad and _native_wgrad_enabled() \
+                and x.dtype == weight.dtype == torch.bfloat16 \
+                and (bias is None or bias.dtype == torch.bfloat16) \
+                and _native_wgrad_rule(rows, weight.shape[0], weight.shape[1]):
+            return _DefaultLinear.apply(x, weight, bias, True)
+        if bias is not None and bias.requires_grad and _bias_grad_enabled() \
+                and x.dtype == weight.dtype == bias.dtype \
+                and x.dtype in (torch.bfloat16, torch.float16, torch.float32) \
+                and rows >= _BIAS_GRAD_MIN_ROWS:
+            return _DefaultLinear.apply(x, weight, bias, False)
     return F.linear(x, weight, bias)
 
 
