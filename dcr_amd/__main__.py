@@ -28,7 +28,8 @@ def main():
     import os
     gates = ["DCR_NATIVE_CONV", "DCR_NATIVE_CONV_BWD", "DCR_NATIVE_GEMM",
              "DCR_NATIVE_WGRAD", "DCR_NATIVE_BIAS_GRAD", "DCR_ATTN_V4", "DCR_ATTN_BWD_V4", "DCR_HIPGRAPH",
-             "DCR_ATTN_V2", "DCR_DEV_ADAMW", "DCR_PROFILE",
+             "DCR_ATTN_V2", "DCR_ATTN_GEN_BWD", "DCR_ATTN_D512",
+             "DCR_DEV_ADAMW", "DCR_PROFILE",
              "DCR_AMD_ALLOW_FALLBACK"]
     active = {g: os.environ[g] for g in gates if g in os.environ}
     desc = active if active else "defaults (native conv on; round-2 drafts off)"

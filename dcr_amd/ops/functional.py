@@ -237,9 +237,10 @@ class _FlashAttentionGen(torch.autograd.Function):
 
 def _attention_math(q, k, v, scale, causal):
     """Composite path (rocBLAS GEMMs + native softmax) for shapes no HIP
-    kernel covers: fp32 inputs, the VAE's single 512-d head, the tiny
-    config's D=32 (and 40/80/160 with grad under DCR_ATTN_GEN_BWD=0).
-    No Triton."""
+    kernel covers: fp32 inputs, the tiny config's D=32, D=512 when causal
+    or with grad (the VAE's frozen no-grad head has attn_fwd_d512; here
+    only under DCR_ATTN_D512=0) and 40/80/160 with grad under
+    DCR_ATTN_GEN_BWD=0. No Triton."""
     count_dispatch('attention_math')
     s = (q.float() @ k.float().transpose(-2, -1)) * scale
     if causal:
@@ -301,6 +302,26 @@ def attention(
             out = fwd(q.reshape(-1, shp[-2], d).contiguous(),
                       k.reshape(-1, k.shape[-2], d).contiguous(),
                       v.reshape(-1, v.shape[-2], d).contiguous())
+            return out.reshape(shp)
+        if q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 \
+                and v.dtype == torch.bfloat16 \
+                and q.shape[-1] == 512 and k.shape[-1] == 512 \
+                and v.shape == k.shape \
+                and not causal and not needs_grad \
+                and os.environ.get("DCR_ATTN_D512", "1") != "0":
+            # the VAE mid-block's single 512-d head (frozen VAE: forward
+            # only). DCR_ATTN_D512=0 restores the composite path, read per
+            # call so one process can A/B.
+            m = require_hip("attn_d512")
+            count_dispatch('attention_d512')
+            if layout == "blhd":
+                return m.attn_fwd_d512(q.contiguous(), k.contiguous(),
+                                       v.contiguous(), scale)
+            shp = q.shape
+            out = m.attn_fwd_d512(q.reshape(-1, shp[-2], 512).contiguous(),
+                                  k.reshape(-1, k.shape[-2], 512).contiguous(),
+                                  v.reshape(-1, v.shape[-2], 512).contiguous(),
+                                  scale)
             return out.reshape(shp)
         if layout == "blhd":
             out = _attention_math(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3),

@@ -1553,6 +1553,260 @@ void attn_fwd_gen_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict_
 }
 
 // ==========================================================================
+// D=512 forward (the VAE mid-block's single head; frozen VAE, so forward
+// only, non-causal, no LSE). The gen template cannot be instantiated at
+// DP=512 (its four LDS arrays would need ~216 KB), and its one-wave-per-
+// 16-rows split would need 64 (Q) + 128 (O) + 16 (S) live registers per
+// lane before any staging. So:
+//  * 64 query rows per block, 8 waves: wave (rg, hf) owns the 16 rows of
+//    row group rg = wid&3 and half hf = wid>>2 of the work on them. Its Q
+//    rows are MFMA A fragments read once from global into registers (16
+//    chunks x 4 VGPRs);
+//  * a whole 64-key K tile [64][512] sits in LDS at pitch 520 (the gen
+//    rule DP+8: 260 dwords/row puts the 16 rows of a ds_read_b128 lane
+//    group on 16 distinct 4-bank groups); the wave accumulates S for keys
+//    hf*32..+32 only;
+//  * the two halves exchange their partial row maxima through LDS, each
+//    writes its 16x32 block of P to sP, and after a barrier both read the
+//    full 16x64 P rows;
+//  * the whole V tile sits transposed [512 dims][64 keys] at pitch 72; the
+//    wave accumulates dims hf*256..+256, so its share of the O accumulator
+//    is 16x256 fp32 = 64 registers;
+//  * K and V have their own buffers, so each tile's global loads are
+//    issued into registers one phase ahead and stored to LDS after the
+//    MFMAs of the phase they overlap: V(n) flies under Q.K(n)^T, K(n+1)
+//    under the softmax and P.V(n). Three barriers per key tile.
+// LDS is 146.5 KiB and a block is 8 waves of up to 256 registers, so one
+// block fills a CU. That is on purpose: the workload grids (B16 L1024 and
+// B4 L4096 are 256 blocks, one 512 px image 64) put at most one block on a
+// CU, so a second resident block to overlap with never arrives, and the
+// overlap has to come from inside the block. Measured alternatives are in
+// hip/README.md. Softmax conventions are attn_fwd_gen_kernel's: -1e30
+// sentinel, key >= Lk masked, P rounded to bf16 (RNE) for PV, row sum in
+// fp32 from the unrounded p (partial sums per half, added once at the end).
+// ==========================================================================
+#define D512 512
+#define D512_KP (D512 + 8)                // K tile row pitch
+
+// K tile [64 keys][512 dims], 512 threads: a wave reads one row's 1 KiB,
+// 8 passes of 8 rows. Rows past `valid` are zero.
+__device__ __forceinline__ void d512_issue_k(const bf16_t* __restrict__ src,
+                                             long rs, int valid, uint4* r) {
+  const int t = threadIdx.x;
+  const int c = (t & 63) * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = (t >> 6) + i * 8;
+    r[i] = make_uint4(0, 0, 0, 0);
+    if (row < valid)
+      r[i] = *reinterpret_cast<const uint4*>(src + (long)row * rs + c);
+  }
+}
+__device__ __forceinline__ void d512_commit_k(const uint4* r,
+                                              short* __restrict__ dst) {
+  const int t = threadIdx.x;
+  const int c = (t & 63) * 8;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    *reinterpret_cast<uint4*>(dst + ((t >> 6) + i * 8) * D512_KP + c) = r[i];
+}
+
+// V tile transposed, 512 threads: dst[dim][key] (pitch 72) = src[key][dim].
+// A thread takes two adjacent keys x 8 dims, four times, and writes each
+// key pair as one dword: half the LDS stores of the 2-byte scatter in the
+// gen kernel's load_vt. r[2i], r[2i+1] = keys r0, r0+1 of unit i.
+__device__ __forceinline__ void d512_issue_v(const bf16_t* __restrict__ src,
+                                             long rs, int valid, uint4* r) {
+  const int t = threadIdx.x;
+  const int lane = t & 63, w = t >> 6;
+  const int r0 = ((w & 1) * 16 + (lane >> 2)) * 2;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = ((w >> 1) * 4 + (lane & 3) + i * 16) * 8;
+    r[2 * i] = make_uint4(0, 0, 0, 0);
+    r[2 * i + 1] = make_uint4(0, 0, 0, 0);
+    if (r0 < valid)
+      r[2 * i] = *reinterpret_cast<const uint4*>(src + (long)r0 * rs + c);
+    if (r0 + 1 < valid)
+      r[2 * i + 1] = *reinterpret_cast<const uint4*>(src + (long)(r0 + 1) * rs + c);
+  }
+}
+__device__ __forceinline__ void d512_commit_v(const uint4* r,
+                                              short* __restrict__ dst) {
+  const int t = threadIdx.x;
+  const int lane = t & 63, w = t >> 6;
+  const int r0 = ((w & 1) * 16 + (lane >> 2)) * 2;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = ((w >> 1) * 4 + (lane & 3) + i * 16) * 8;
+    const unsigned av[4] = {r[2 * i].x, r[2 * i].y, r[2 * i].z, r[2 * i].w};
+    const unsigned bv[4] = {r[2 * i + 1].x, r[2 * i + 1].y, r[2 * i + 1].z,
+                            r[2 * i + 1].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned* d0 = reinterpret_cast<unsigned*>(dst + (c + 2 * j) * PITCH + r0);
+      unsigned* d1 = reinterpret_cast<unsigned*>(dst + (c + 2 * j + 1) * PITCH + r0);
+      *d0 = (av[j] & 0xffffu) | (bv[j] << 16);
+      *d1 = (av[j] >> 16) | (bv[j] & 0xffff0000u);
+    }
+  }
+}
+
+// grid (ceil(Lq/64), BH), block 512.
+__global__ __launch_bounds__(512)
+void attn_fwd_d512_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                          const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
+                          int Lq, int Lk, int H, float scale) {
+  __shared__ short sK[TILE * D512_KP];    // [key][dim]
+  __shared__ short sVT[D512 * PITCH];     // [dim][key]
+  __shared__ short sP[TILE * PITCH];      // [qrow][key]
+  __shared__ float sX[2][TILE];           // per-half row max / row sum
+
+  const int bh = blockIdx.y;
+  const int b = bh / H, h = bh % H;
+  const int q0 = blockIdx.x * TILE;
+  const long rs = (long)H * D512;         // [B,L,H,D] row stride
+  const bf16_t* qp = q + (((long)b * Lq + q0) * H + h) * D512;
+  const bf16_t* kp = k + ((long)b * Lk * H + h) * D512;
+  const bf16_t* vp = v + ((long)b * Lk * H + h) * D512;
+  bf16_t* op = o + ((long)b * Lq * H + h) * D512;
+
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int wid = t >> 6;
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int wrow0 = (wid & 3) * 16;
+  const int hf = wid >> 2;
+  constexpr int NK = D512 / 32;           // 16 contraction chunks
+  constexpr int ND = D512 / 32;           // 16 of the 32 output d-subtiles
+
+  bf16x8 qf[NK];
+  {
+    const bf16_t* qrow = qp + (long)(wrow0 + l16) * rs + kgrp * 8;
+    const bool qvalid = q0 + wrow0 + l16 < Lq;
+#pragma unroll
+    for (int ck = 0; ck < NK; ++ck) {
+      uint4 a = make_uint4(0, 0, 0, 0);
+      if (qvalid) a = *reinterpret_cast<const uint4*>(qrow + ck * 32);
+      qf[ck] = *reinterpret_cast<bf16x8*>(&a);
+    }
+  }
+
+  float row_max[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
+  float row_sum[4] = {0.f, 0.f, 0.f, 0.f};   // this half's keys only
+  f32x4_t acc_o[ND];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) acc_o[i] = {0.f, 0.f, 0.f, 0.f};
+
+  uint4 stage[8];                         // one tile's share in flight
+  d512_issue_k(kp, rs, Lk, stage);
+  d512_commit_k(stage, sK);
+  __syncthreads();
+
+  for (int kv0 = 0; kv0 < Lk; kv0 += TILE) {
+    const int valid = Lk - kv0;
+    d512_issue_v(vp + (long)kv0 * rs, rs, valid, stage);
+
+    // S[16 rows][keys hf*32 .. +32]
+    f32x4_t s_frag[2];
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns) {
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ck = 0; ck < NK; ++ck) {
+        bf16x8 kf = *reinterpret_cast<const bf16x8*>(
+            sK + (hf * 32 + ns * 16 + l16) * D512_KP + ck * 32 + kgrp * 8);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[ck], kf, acc, 0, 0, 0);
+      }
+      s_frag[ns] = acc;
+    }
+
+    float tile_max[4] = {-1e30f, -1e30f, -1e30f, -1e30f};
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns) {
+      const int key = kv0 + hf * 32 + ns * 16 + l16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float sv = s_frag[ns][r] * scale;
+        if (key >= Lk) sv = -1e30f;
+        s_frag[ns][r] = sv;
+        tile_max[r] = fmaxf(tile_max[r], sv);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      tile_max[r] = qmax(tile_max[r]);
+      if (l16 == 0) sX[hf][wrow0 + kgrp * 4 + r] = tile_max[r];
+    }
+    d512_commit_v(stage, sVT);
+    __syncthreads();            // partial maxima, V^T; all reads of sK done
+
+    // the next K tile flies under the softmax and P.V (all zero past Lk)
+    d512_issue_k(kp + (long)(kv0 + TILE) * rs, rs, valid - TILE, stage);
+
+    float alpha[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float tm = fmaxf(tile_max[r], sX[hf ^ 1][wrow0 + kgrp * 4 + r]);
+      float mnew = fmaxf(row_max[r], tm);
+      alpha[r] = (mnew <= -1e29f) ? 1.f : __expf(row_max[r] - mnew);
+      row_max[r] = mnew;
+    }
+
+    float psum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ns = 0; ns < 2; ++ns) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float pv = (s_frag[ns][r] <= -1e29f)
+                       ? 0.f : __expf(s_frag[ns][r] - row_max[r]);
+        psum[r] += pv;
+        sP[(wrow0 + kgrp * 4 + r) * PITCH + hf * 32 + ns * 16 + l16] =
+            f2bf_rne(pv);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) row_sum[r] = row_sum[r] * alpha[r] + qsum(psum[r]);
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc_o[i][r] *= alpha[r];
+    __syncthreads();            // both halves of the P rows
+
+    bf16x8 pf0 = frag(sP, wrow0 + l16, kgrp * 8);
+    bf16x8 pf1 = frag(sP, wrow0 + l16, kgrp * 8 + 32);
+#pragma unroll
+    for (int ds_ = 0; ds_ < ND; ++ds_) {
+      const int drow = hf * 256 + ds_ * 16 + l16;
+      acc_o[ds_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          pf0, frag(sVT, drow, kgrp * 8), acc_o[ds_], 0, 0, 0);
+      acc_o[ds_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          pf1, frag(sVT, drow, kgrp * 8 + 32), acc_o[ds_], 0, 0, 0);
+    }
+    d512_commit_k(stage, sK);
+    __syncthreads();            // next K tile; all reads of sVT, sP, sX done
+  }
+
+  // total row sum = this half's + the other half's (same running max)
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (l16 == 0) sX[hf][wrow0 + kgrp * 4 + r] = row_sum[r];
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qrow = q0 + wrow0 + kgrp * 4 + r;
+    if (qrow >= Lq) continue;
+    const float sum = row_sum[r] + sX[hf ^ 1][wrow0 + kgrp * 4 + r];
+    const float inv = (sum > 0.f) ? 1.f / sum : 0.f;
+#pragma unroll
+    for (int ds_ = 0; ds_ < ND; ++ds_)
+      op[(long)qrow * rs + hf * 256 + ds_ * 16 + l16] =
+          __float2bfloat16(acc_o[ds_][r] * inv);
+  }
+}
+
+// ==========================================================================
 // Generalized-head-dim backward (SD-1.x finetune: head_dim 40/80/160).
 // The v1 FlashAttention-2 split (64x64 tiles, 4 waves, no atomics: dK/dV
 // owned by key tiles, dQ by query tiles) with two changes for large D:
@@ -1966,6 +2220,17 @@ void attn_fwd_gen_launch(const void* q, const void* k, const void* v, void* o,
     default:
       break;  // binding guards D
   }
+}
+
+// D=512 forward (VAE mid-block head): non-causal, no LSE
+void attn_fwd_d512_launch(const void* q, const void* k, const void* v, void* o,
+                          int BH, int Lq, int Lk, int H, float scale,
+                          hipStream_t s) {
+  dim3 grid((Lq + TILE - 1) / TILE, BH), block(512);
+  hipLaunchKernelGGL(dcr_attn::attn_fwd_d512_kernel, grid, block, 0, s,
+                     (const dcr_attn::bf16_t*)q, (const dcr_attn::bf16_t*)k,
+                     (const dcr_attn::bf16_t*)v, (dcr_attn::bf16_t*)o, Lq, Lk,
+                     H, scale);
 }
 
 // generalized head-dim backward (SD-1.x finetune 40/80/160): delta, then

@@ -6,6 +6,8 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <climits>
+
 #include "dcr_launchers.h"
 
 using namespace dcr;
@@ -521,6 +523,52 @@ std::vector<at::Tensor> attn_fwd_gen_lse(at::Tensor q, at::Tensor k,
   return {o, lse};
 }
 
+// D=512 forward (VAE mid-block's single head). q/k/v: [B, L, H, 512] or
+// packed [BH, L, 512]. Everything is checked here, before any launch.
+static void attn_d512_dims(const at::Tensor& q, const at::Tensor& k,
+                           const at::Tensor& v, int64_t& B, int64_t& H,
+                           int64_t& Lq, int64_t& Lk) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() &&
+              q.scalar_type() == at::kBFloat16 &&
+              k.scalar_type() == at::kBFloat16 &&
+              v.scalar_type() == at::kBFloat16,
+              "attn_fwd_d512: bf16 CUDA tensors only");
+  TORCH_CHECK(q.get_device() == k.get_device() &&
+              q.get_device() == v.get_device(),
+              "attn_fwd_d512: q/k/v on different devices");
+  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous(),
+              "attn_fwd_d512: q/k/v must be contiguous");
+  TORCH_CHECK(q.dim() == 3 || q.dim() == 4,
+              "attn_fwd_d512: [B,L,H,512] or [BH,L,512]");
+  TORCH_CHECK(k.dim() == q.dim(), "attn_fwd_d512: q/k rank mismatch");
+  TORCH_CHECK(q.size(-1) == 512 && k.size(-1) == 512,
+              "attn_fwd_d512: head_dim 512 only");
+  TORCH_CHECK(k.sizes() == v.sizes(), "attn_fwd_d512: k/v shape mismatch");
+  TORCH_CHECK(k.size(0) == q.size(0), "attn_fwd_d512: q/k batch mismatch");
+  B = q.size(0); Lq = q.size(1); Lk = k.size(1);
+  H = 1;
+  if (q.dim() == 4) {
+    H = q.size(2);
+    TORCH_CHECK(k.size(2) == H, "attn_fwd_d512: q/k head count mismatch");
+  }
+  TORCH_CHECK(Lk > 0 || q.numel() == 0, "attn_fwd_d512: no keys");
+  TORCH_CHECK(Lq <= INT_MAX - 64 && Lk <= INT_MAX - 64 && H <= INT_MAX &&
+              B * H <= 65535,
+              "attn_fwd_d512: grid out of range (B*H <= 65535)");
+}
+
+at::Tensor attn_fwd_d512(at::Tensor q, at::Tensor k, at::Tensor v,
+                         double scale) {
+  int64_t B, H, Lq, Lk;
+  attn_d512_dims(q, k, v, B, H, Lq, Lk);
+  auto o = at::empty_like(q);
+  if (q.numel() == 0) return o;
+  attn_fwd_d512_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                       (int)(B * H), (int)Lq, (int)Lk, (int)H, (float)scale,
+                       cur_stream());
+  return o;
+}
+
 std::vector<at::Tensor> attn_bwd_gen(at::Tensor q, at::Tensor k, at::Tensor v,
                                      at::Tensor o, at::Tensor dO,
                                      at::Tensor lse, double scale,
@@ -876,6 +924,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_fwd_gen", &attn_fwd_gen);
   mod.def("attn_fwd_gen_lse", &attn_fwd_gen_lse);
+  mod.def("attn_fwd_d512", &attn_fwd_d512);
   mod.def("attn_bwd_gen", &attn_bwd_gen);
   mod.def("attn_fwd_v2", &attn_fwd_v2);
   mod.def("attn_fwd_v3", &attn_fwd_v3);

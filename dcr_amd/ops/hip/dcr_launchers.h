@@ -108,6 +108,10 @@ void attn_fwd_v4_launch(const void* q, const void* k, const void* v, void* o,
 void attn_fwd_gen_launch(const void* q, const void* k, const void* v, void* o,
                          float* lse, int BH, int Lq, int Lk, int H, int D,
                          float scale, bool causal, hipStream_t s);
+// D=512 forward (VAE mid-block's single head): non-causal, no LSE
+void attn_fwd_d512_launch(const void* q, const void* k, const void* v, void* o,
+                          int BH, int Lq, int Lk, int H, float scale,
+                          hipStream_t s);
 // generalized head-dim backward (40/80/160): delta + dK/dV + dQ, no atomics
 void attn_bwd_gen_launch(const void* q, const void* k, const void* v,
                          const void* o, const void* dO, const float* lse,
