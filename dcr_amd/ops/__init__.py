@@ -104,5 +104,6 @@ from .functional import (  # noqa: E402,F401
     get_velocity,
     cfg_combine,
     lincomb,
+    patch_maxsim,
 )
 from .adamw import FusedAdamW  # noqa: E402,F401

@@ -28,6 +28,7 @@ SOURCES = [
     HIP_DIR / "conv_nhwc.hip",
     HIP_DIR / "conv_nhwc_bwd.hip",
     HIP_DIR / "gemm.hip",
+    HIP_DIR / "maxsim.hip",
 ]
 
 

@@ -407,6 +407,96 @@ def lincomb(x: torch.Tensor, y: torch.Tensor, a: float, b: float,
     return out.to(x.dtype)
 
 
+# --------------------------------------------------------------------------
+# Patch max-similarity (split-product retrieval, stype="cross")
+# --------------------------------------------------------------------------
+def _bf16_split(x: torch.Tensor):
+    """x (fp32) as hi + lo with both in bf16: hi = bf16(x), lo = bf16(x - hi).
+    hi + lo carries 16 significand bits of x."""
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    return hi, lo
+
+
+def _maxsim_operand(x: torch.Tensor, precision: str, side: str) -> torch.Tensor:
+    """The bf16 [rows, patches, K'] operand the kernel contracts.
+
+    "bf16": x rounded to bf16, K' = C. "high": the K-concatenation
+    [hi | hi | lo] for side "a" and [hi | lo | hi] for side "b", K' = 3C, so
+    one fp32-accumulating product sums hi.hi + hi.lo + lo.hi. C is padded
+    with zeros to a multiple of 8 first."""
+    pad = -x.shape[-1] % 8
+    if precision == "bf16":
+        x = x.to(torch.bfloat16)
+        if pad:
+            x = F.pad(x, (0, pad))
+        return x.contiguous()
+    x = x.float()
+    if pad:
+        x = F.pad(x, (0, pad))
+    hi, lo = _bf16_split(x)
+    parts = (hi, hi, lo) if side == "a" else (hi, lo, hi)
+    return torch.cat(parts, dim=-1)
+
+
+def maxsim_operands(a: torch.Tensor, b: torch.Tensor, precision: str = "high"):
+    """(A', B') in bf16 as `patch_maxsim` hands them to the kernel."""
+    if precision not in ("high", "bf16"):
+        raise ValueError(f"precision must be 'high' or 'bf16', not {precision!r}")
+    return _maxsim_operand(a, precision, "a"), _maxsim_operand(b, precision, "b")
+
+
+def _maxsim_ref(a2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """CPU path: fp32 products of the transformed operands, max over patch
+    pairs. One row of `a` at a time, so the intermediate is [M*Q, P] and the
+    way callers chunk the rows cannot change a bit of the result."""
+    n, p, k = a2.shape
+    m, q, _ = b2.shape
+    bf = b2.float().reshape(m * q, k)
+    out = torch.empty(n, m, dtype=torch.float32, device=a2.device)
+    for i in range(n):
+        s = bf @ a2[i].float().t()               # [M*Q, P]
+        out[i] = s.reshape(m, q * p).amax(dim=1)
+    return out
+
+
+def patch_maxsim(a: torch.Tensor, b: torch.Tensor, *, precision: str = "high",
+                 chunk: Optional[int] = None) -> torch.Tensor:
+    """out[n, m] = max over patch pairs (p, q) of <a[n, p, :], b[m, q, :]>.
+
+    a [N, P, C], b [M, Q, C], any float dtype; returns fp32 [N, M]. On the
+    GPU one fused kernel (dcr_amd/ops/hip/maxsim.hip) contracts in bf16 MFMA
+    with fp32 accumulation and reduces the scores without storing them.
+    precision="bf16" rounds both operands to bf16; "high" (default) contracts
+    the bf16 hi/lo split of both (3x the FLOPs, fp32-grade scores). `chunk`
+    is the number of rows of `a` per launch (bounds the transformed copy of
+    `a`); it does not change the result. CPU tensors take the same operand
+    transformation and an fp32 matmul."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != b.shape[2]:
+        raise ValueError("patch_maxsim: a [N, P, C] and b [M, Q, C] expected, "
+                         f"got {tuple(a.shape)} and {tuple(b.shape)}")
+    if precision not in ("high", "bf16"):
+        raise ValueError(f"precision must be 'high' or 'bf16', not {precision!r}")
+    if chunk is not None and chunk < 1:
+        raise ValueError("patch_maxsim: chunk must be >= 1")
+    n, m = a.shape[0], b.shape[0]
+    if n == 0 or m == 0:
+        return torch.empty(n, m, dtype=torch.float32, device=a.device)
+    if a.shape[1] == 0 or b.shape[1] == 0 or a.shape[2] == 0:
+        raise ValueError("patch_maxsim: P, Q and C must be >= 1")
+    step = n if chunk is None else chunk
+    b2 = _maxsim_operand(b, precision, "b")
+    run = _maxsim_ref
+    if use_hip(a):
+        mod = require_hip("patch_maxsim")
+        if mod is not None:  # None: debug fallback on GPU
+            count_dispatch('patch_maxsim')
+            run = mod.patch_maxsim
+    outs = [run(_maxsim_operand(a[i:i + step], precision, "a"), b2)
+            for i in range(0, n, step)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
 def cfg_combine(eps_uncond: torch.Tensor, eps_text: torch.Tensor, scale: float) -> torch.Tensor:
     """Classifier-free guidance: eps_u + s * (eps_t - eps_u)."""
     from . import ext

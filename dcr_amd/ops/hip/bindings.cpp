@@ -7,6 +7,8 @@
 #include <ATen/cuda/CUDAContext.h>
 
 #include <climits>
+#include <cstdint>
+#include <limits>
 
 #include "dcr_launchers.h"
 
@@ -909,8 +911,43 @@ std::vector<at::Tensor> linear_wgrad(at::Tensor dy, at::Tensor x, bool want_db,
   return {dw};
 }
 
+// ---------------------------------------------------------------- maxsim
+// out[n, m] = max over patch pairs (p, q) of <A[n, p, :], B[m, q, :]>, fp32.
+// One fused launch: the [N*P, M*Q] score matrix is never stored.
+at::Tensor patch_maxsim(at::Tensor A, at::Tensor B) {
+  TORCH_CHECK(A.is_cuda() && B.is_cuda() && A.device() == B.device(),
+              "patch_maxsim: CUDA tensors on one device expected");
+  TORCH_CHECK(A.scalar_type() == at::kBFloat16 &&
+              B.scalar_type() == at::kBFloat16, "patch_maxsim: bf16 only");
+  TORCH_CHECK(A.dim() == 3 && B.dim() == 3,
+              "patch_maxsim: A [N, P, C] and B [M, Q, C] expected");
+  TORCH_CHECK(A.is_contiguous() && B.is_contiguous(),
+              "patch_maxsim: contiguous operands expected");
+  const int64_t N = A.size(0), P = A.size(1), C = A.size(2);
+  const int64_t M = B.size(0), Q = B.size(1);
+  TORCH_CHECK(B.size(2) == C, "patch_maxsim: C mismatch");
+  TORCH_CHECK(C >= 8 && C % 8 == 0, "patch_maxsim: C % 8 != 0");
+  TORCH_CHECK(P >= 1 && Q >= 1, "patch_maxsim: P >= 1 and Q >= 1 expected");
+  TORCH_CHECK(P < (1LL << 30) && Q < (1LL << 30) && C < (1LL << 30),
+              "patch_maxsim: P, Q, C must stay below 2^30");
+  auto out = at::full({N, M}, -std::numeric_limits<float>::infinity(),
+                      A.options().dtype(at::kFloat));
+  if (N == 0 || M == 0) return out;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
+              "patch_maxsim: operands must be 16-byte aligned");
+  const int64_t tiles = ((N * P + 127) / 128) * ((M * Q + 127) / 128);
+  TORCH_CHECK(tiles < (1LL << 31),
+              "patch_maxsim: too many score tiles for one launch; "
+              "pass fewer rows of A per call");
+  patch_maxsim_launch(A.data_ptr(), B.data_ptr(), out.data_ptr<float>(), N, M,
+                      (int)P, (int)Q, (int)C, cur_stream());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gemm_bf16", &gemm_bf16);
+  mod.def("patch_maxsim", &patch_maxsim);
   mod.def("linear_wgrad", &linear_wgrad, pybind11::arg("dy2d"),
           pybind11::arg("x2d"), pybind11::arg("want_db"),
           pybind11::arg("split") = 0, pybind11::arg("tile") = 0);

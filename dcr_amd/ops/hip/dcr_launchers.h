@@ -168,4 +168,10 @@ void linear_wgrad_launch(const void* dy, const void* x, float* slab,
                          int tile, int split, int chunks_per_slice,
                          hipStream_t st);
 
+// maxsim.hip — out[n,m] = max_{p,q} <A[n,p,:], B[m,q,:]>; A [N,P,K] and
+// B [M,Q,K] bf16 contiguous, K % 8 == 0; out [N,M] fp32 pre-filled with
+// -inf (partial maxima are combined with atomics). N, M >= 1.
+void patch_maxsim_launch(const void* A, const void* B, float* out, long N,
+                         long M, int P, int Q, int K, hipStream_t st);
+
 }  // namespace dcr

@@ -34,13 +34,23 @@ def sim_matrix(a: torch.Tensor, b: torch.Tensor,
 
 
 def einsum_in_chunks(feat_a: torch.Tensor, feat_b: torch.Tensor,
-                     chunk: int = 64, stype: str = "cross") -> torch.Tensor:
+                     chunk: int = 64, stype: str = "cross",
+                     precision: str = "high") -> torch.Tensor:
     """Patch-wise 'splitloss' similarity; feats are [N, C, P] per-patch
     descriptors. stype='cross' takes the max over all patch PAIRS
     (reference's einsum_in_chunks intent, diff_retrieval.py:643-662,
     'ncp,mdp->nmcd' in its layout); stype='' matches the reference's live
     splitloss path (diff_retrieval.py:397-400): same-patch dot, max over
-    patches."""
+    patches.
+
+    stype='cross' on CUDA tensors runs the fused HIP kernel
+    (dcr_amd.ops.patch_maxsim), which never builds the [chunk, M, P, Q]
+    block; `precision` ('high' or 'bf16') is that op's and has no effect
+    on any other path."""
+    if stype == "cross" and feat_a.is_cuda and feat_b.is_cuda:
+        from ..ops import patch_maxsim
+        return patch_maxsim(feat_a.transpose(1, 2), feat_b.transpose(1, 2),
+                            precision=precision, chunk=max(1, chunk))
     sims = []
     for i in range(0, feat_a.shape[0], chunk):
         a = feat_a[i:i + chunk].float()

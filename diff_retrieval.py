@@ -66,6 +66,12 @@ def parse_args():
     p.add_argument("--keeppredictor", action="store_true")
     p.add_argument("-ssp", "--sim_save_path", type=str, default="./similarityscores/")
     p.add_argument("--einsum_chunks", default=30, type=int)
+    p.add_argument("--maxsim_precision", default="high",
+                   choices=["high", "bf16"],
+                   help="splitloss with --stype cross on a GPU (fused patch "
+                        "max-similarity kernel): 'high' contracts a bf16 "
+                        "hi/lo split of the features (fp32-grade scores, 3x "
+                        "the FLOPs), 'bf16' rounds them to bf16")
     p.add_argument("--dontsave", action="store_true")
     p.add_argument("--num_matches", default=4, type=int)
     p.add_argument("--imsize", default=224, type=int)
@@ -115,8 +121,14 @@ def build_backbone(args, device):
 @torch.no_grad()
 def _patch_features(model, loader, device, args):
     """[N, D, P] L2-normalized per-patch descriptors: ViT token features
-    (get_intermediate_layers) or the CNN's final spatial map."""
+    (get_intermediate_layers) or the CNN's final spatial map. They go to
+    the CPU, except for --stype cross on a GPU: the fused max-similarity
+    kernel takes them on the device (bf16 under --maxsim_precision bf16,
+    else fp32)."""
     import torch.nn.functional as F_
+    on_device = args.stype == "cross" and device.type == "cuda"
+    keep_dtype = torch.bfloat16 if args.maxsim_precision == "bf16" \
+        else torch.float32
     feats = []
     for batch in loader:
         imgs = batch[0].to(device)
@@ -128,7 +140,8 @@ def _patch_features(model, loader, device, args):
             f = fm.flatten(2)
         else:
             f = model(imgs)[..., None]
-        feats.append(F_.normalize(f, dim=1).cpu())
+        f = F_.normalize(f, dim=1)
+        feats.append(f.to(keep_dtype) if on_device else f.cpu())
     return torch.cat(feats)
 
 
@@ -185,10 +198,12 @@ def main():
         vp_ = _patch_features(model, loader(val_ds), device, args)
         sim = einsum_in_chunks(qp_, vp_, chunk=max(1, len(query_ds) //
                                                    max(1, args.einsum_chunks)),
-                               stype=args.stype)
+                               stype=args.stype,
+                               precision=args.maxsim_precision)
         sim_tt = einsum_in_chunks(vp_, vp_, chunk=max(1, len(val_ds) //
                                                       max(1, args.einsum_chunks)),
-                                  stype=args.stype)
+                                  stype=args.stype,
+                                  precision=args.maxsim_precision)
     else:
         sim = sim_matrix(val_f, query_f).t()    # [n_gen, n_train] (rocBLAS)
         sim_tt = sim_matrix(val_f, val_f)       # [n_train, n_train]
