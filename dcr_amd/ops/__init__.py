@@ -105,5 +105,6 @@ from .functional import (  # noqa: E402,F401
     cfg_combine,
     lincomb,
     patch_maxsim,
+    topk_sim,
 )
 from .adamw import FusedAdamW  # noqa: E402,F401

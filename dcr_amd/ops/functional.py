@@ -497,6 +497,78 @@ def patch_maxsim(a: torch.Tensor, b: torch.Tensor, *, precision: str = "high",
     return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
 
+# --------------------------------------------------------------------------
+# Top-k similarity search (embedding search)
+# --------------------------------------------------------------------------
+TOPK_SIM_MAX_K = 16   # list capacity of the fused kernel
+
+
+def topk_sim_operands(q: torch.Tensor, x: torch.Tensor, precision: str = "high"):
+    """(Q', X') in bf16 as `topk_sim` hands them to the kernel."""
+    if precision not in ("high", "bf16"):
+        raise ValueError(f"precision must be 'high' or 'bf16', not {precision!r}")
+    return _maxsim_operand(q, precision, "a"), _maxsim_operand(x, precision, "b")
+
+
+def _topk_sim_ref(q2: torch.Tensor, x2: torch.Tensor, k: int):
+    """CPU path: fp32 products of the transformed operands, then the ordering
+    rule: higher score first, the lower index first among equal scores, NaN
+    never taken. Columns are in index order already, so one stable descending
+    sort is the stable-by-index-then-stable-by-score order."""
+    xf = x2.float()
+    vals, idxs = [], []
+    for i in range(0, q2.shape[0], 1024):
+        s = q2[i:i + 1024].float() @ xf.t()
+        s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+        v, ix = torch.sort(s, dim=1, descending=True, stable=True)
+        vals.append(v[:, :k].contiguous())
+        idxs.append(ix[:, :k].contiguous())
+    return torch.cat(vals, dim=0), torch.cat(idxs, dim=0)
+
+
+def topk_sim(q: torch.Tensor, x: torch.Tensor, k: int, *,
+             precision: str = "bf16"):
+    """The k best rows of x for every row of q by dot product.
+
+    q [Nq, D], x [Nx, D], any float dtype; returns (scores fp32 [Nq, k],
+    idx int64 [Nq, k]), higher score first and the lower index first among
+    equal scores; a NaN score is never returned. On the GPU one fused kernel
+    (dcr_amd/ops/hip/topk_sim.hip) contracts in bf16 MFMA with fp32
+    accumulation and keeps the k best per row in registers: the [Nq, Nx]
+    score matrix is never stored, and the result does not depend on how the
+    caller chunks the query rows. precision="bf16" rounds both operands to
+    bf16; "high" contracts the bf16 hi/lo split of both (3x the FLOPs,
+    fp32-grade scores). The kernel holds k <= 16. CPU tensors take the same
+    operand transformation and an fp32 matmul."""
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1] \
+            or q.shape[1] == 0:
+        raise ValueError("topk_sim: q [Nq, D] and x [Nx, D] with D >= 1 "
+                         f"expected, got {tuple(q.shape)} and {tuple(x.shape)}")
+    if precision not in ("high", "bf16"):
+        raise ValueError(f"precision must be 'high' or 'bf16', not {precision!r}")
+    k = int(k)
+    if k < 1:
+        raise ValueError("topk_sim: k must be >= 1")
+    if k > x.shape[0]:
+        raise ValueError(f"topk_sim: k = {k} exceeds the {x.shape[0]} index rows")
+    if q.shape[0] == 0:
+        return (torch.empty(0, k, dtype=torch.float32, device=q.device),
+                torch.empty(0, k, dtype=torch.long, device=q.device))
+    if use_hip(q):
+        if k > TOPK_SIM_MAX_K:
+            raise ValueError(
+                f"topk_sim: the fused kernel holds k <= {TOPK_SIM_MAX_K}, got "
+                f"{k}; callers fall back to the library path (matmul + topk)")
+        mod = require_hip("topk_sim")
+        if mod is not None:  # None: debug fallback on GPU
+            count_dispatch('topk_sim')
+            scores, idx = mod.topk_sim(_maxsim_operand(q, precision, "a"),
+                                       _maxsim_operand(x, precision, "b"), k)
+            return scores, idx
+    return _topk_sim_ref(_maxsim_operand(q, precision, "a"),
+                         _maxsim_operand(x, precision, "b"), k)
+
+
 def cfg_combine(eps_uncond: torch.Tensor, eps_text: torch.Tensor, scale: float) -> torch.Tensor:
     """Classifier-free guidance: eps_u + s * (eps_t - eps_u)."""
     from . import ext

@@ -945,7 +945,57 @@ at::Tensor patch_maxsim(at::Tensor A, at::Tensor B) {
   return out;
 }
 
+// ---------------------------------------------------------------- topk_sim
+// Per row of q [Nq, D] the m best (score, column) pairs of q x^T over
+// x [Nx, D], higher score first and the lower column first among equals:
+// {scores fp32 [Nq, m], idx int64 [Nq, m]}. The score matrix is never
+// stored. stripes = 0 takes the launcher's rule; any value gives the same
+// bits.
+std::vector<at::Tensor> topk_sim(at::Tensor q, at::Tensor x, int64_t m,
+                                 int64_t stripes) {
+  TORCH_CHECK(q.is_cuda() && x.is_cuda() && q.device() == x.device(),
+              "topk_sim: CUDA tensors on one device expected");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 &&
+              x.scalar_type() == at::kBFloat16, "topk_sim: bf16 only");
+  TORCH_CHECK(q.dim() == 2 && x.dim() == 2,
+              "topk_sim: q [Nq, D] and x [Nx, D] expected");
+  const int64_t Nq = q.size(0), D = q.size(1), Nx = x.size(0);
+  TORCH_CHECK(Nx < (1LL << 31), "topk_sim: Nx must stay below 2^31");
+  TORCH_CHECK(Nq < (1LL << 31),
+              "topk_sim: pass fewer than 2^31 query rows per call");
+  TORCH_CHECK(q.is_contiguous() && x.is_contiguous(),
+              "topk_sim: contiguous operands expected");
+  TORCH_CHECK(x.size(1) == D, "topk_sim: D mismatch");
+  TORCH_CHECK(D >= 8 && D % 8 == 0 && D < (1LL << 30),
+              "topk_sim: D % 8 != 0");
+  TORCH_CHECK(m >= 1 && m <= 16, "topk_sim: 1 <= m <= 16 expected");
+  TORCH_CHECK(m <= Nx, "topk_sim: m exceeds the number of index rows");
+  TORCH_CHECK(stripes >= 0 && stripes < (1LL << 24),
+              "topk_sim: stripes out of range");
+  auto scores = at::empty({Nq, m}, q.options().dtype(at::kFloat));
+  auto idx = at::empty({Nq, m}, q.options().dtype(at::kLong));
+  if (Nq == 0) return {scores, idx};
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "topk_sim: operands must be 16-byte aligned");
+  int cap, ns;
+  long tps;
+  topk_sim_plan(Nq, Nx, (int)m, (int)stripes, &cap, &ns, &tps);
+  TORCH_CHECK(((Nq + 127) / 128) * ns < (1LL << 31),
+              "topk_sim: too many blocks for one launch; pass fewer query "
+              "rows per call");
+  auto part_s = at::empty({Nq, 2 * ns, cap}, q.options().dtype(at::kFloat));
+  auto part_i = at::empty({Nq, 2 * ns, cap}, q.options().dtype(at::kInt));
+  topk_sim_launch(q.data_ptr(), x.data_ptr(), part_s.data_ptr<float>(),
+                  part_i.data_ptr<int>(), scores.data_ptr<float>(),
+                  reinterpret_cast<long*>(idx.data_ptr<int64_t>()), Nq, Nx,
+                  (int)D, (int)m, cap, ns, tps, cur_stream());
+  return {scores, idx};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("topk_sim", &topk_sim, pybind11::arg("q"), pybind11::arg("x"),
+          pybind11::arg("m"), pybind11::arg("stripes") = 0);
   mod.def("gemm_bf16", &gemm_bf16);
   mod.def("patch_maxsim", &patch_maxsim);
   mod.def("linear_wgrad", &linear_wgrad, pybind11::arg("dy2d"),

@@ -174,4 +174,17 @@ void linear_wgrad_launch(const void* dy, const void* x, float* slab,
 void patch_maxsim_launch(const void* A, const void* B, float* out, long N,
                          long M, int P, int Q, int K, hipStream_t st);
 
+// topk_sim.hip — per row of Qm [Nq,K] the m best (score, column) pairs of
+// Qm X^T over X [Nx,K]; bf16 contiguous, K % 8 == 0, 1 <= m <= 16, m <= Nx,
+// Nx < 2^31. topk_sim_plan gives the list capacity (1/4/8/16 >= m), the
+// stripe count (stripes_req > 0 forces it, clamped to the index tiles) and
+// the 128-row tiles per stripe. part_s / part_i: Nq * 2*stripes * cap
+// elements, uninitialised. out_s / out_i: [Nq, m]. No atomics.
+void topk_sim_plan(long Nq, long Nx, int m, int stripes_req, int* cap,
+                   int* stripes, long* tiles_per_stripe);
+void topk_sim_launch(const void* Qm, const void* X, float* part_s, int* part_i,
+                     float* out_s, long* out_i, long Nq, long Nx, int K, int m,
+                     int cap, int stripes, long tiles_per_stripe,
+                     hipStream_t st);
+
 }  // namespace dcr

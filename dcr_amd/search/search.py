@@ -14,6 +14,7 @@ feature-matrix traffic — and every rank reduces to the global top-k.
 """
 from __future__ import annotations
 
+import os
 import pickle
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
@@ -22,22 +23,52 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .. import ops
 from ..parallel import dist as dist_utils
 
 
+SEARCH_PRECISIONS = ("high", "bf16", "fp32")
+_STREAM_CANDIDATES = 5   # fused candidates per chunk, re-ranked in fp32
+
+
+def _fused_search_enabled() -> bool:
+    """DCR_FUSED_SEARCH=0 restores the library path (GEMM + topk); read per
+    call so one process can A/B."""
+    return os.environ.get("DCR_FUSED_SEARCH", "1") != "0"
+
+
 def stream_top1(query: torch.Tensor, chunk_files: Sequence[str | Path],
-                device: Optional[str] = None, query_chunks: int = 1
+                device: Optional[str] = None, query_chunks: int = 1,
+                precision: Optional[str] = None
                 ) -> Tuple[np.ndarray, List[str]]:
     """Single-process streaming search (reference semantics).
 
     query: [Q, D] (L2-normed) generation embeddings.
     Returns (scores [Q], keys [Q]) of the best LAION match per query.
+
+    precision: on a GPU, None means "high": per chunk the fused top-k kernel
+    (ops.topk_sim, no score matrix) picks 5 candidates per query from the
+    bf16 hi/lo split product and an fp32 re-rank of those gives the returned
+    exact fp32 score. "bf16" does the same with bf16-rounded operands.
+    "fp32", or any CPU device, is the plain fp32 GEMM + max. The running
+    best stays on the device; keys are resolved once at the end. The first
+    chunk wins ties.
     """
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
+    on_gpu = torch.device(device).type == "cuda"
+    if precision is None:
+        precision = "high" if on_gpu else "fp32"
+    if precision not in SEARCH_PRECISIONS:
+        raise ValueError(f"precision must be one of {SEARCH_PRECISIONS}, "
+                         f"not {precision!r}")
+    fused = on_gpu and precision != "fp32" and _fused_search_enabled()
     query = query.to(device).float()
     Q = query.shape[0]
     best = torch.full((Q,), -1e30, device=device)
-    best_key: List[Optional[str]] = [None] * Q
+    best_chunk = torch.full((Q,), -1, dtype=torch.long, device=device)
+    best_row = torch.zeros((Q,), dtype=torch.long, device=device)
+    index_lists: List[Sequence] = []
+    step = max(1, Q // query_chunks)
 
     for f in chunk_files:
         try:
@@ -47,17 +78,33 @@ def stream_top1(query: torch.Tensor, chunk_files: Sequence[str | Path],
             continue  # unreadable chunk: skip (reference :51-55 intent)
         feats = torch.from_numpy(np.asarray(blob["features"], dtype=np.float32)) \
             .to(device)
-        idxs = blob["indexes"]
-        for qs in range(0, Q, max(1, Q // query_chunks)):
-            qe = min(Q, qs + max(1, Q // query_chunks))
-            sim = feats @ query[qs:qe].t()          # [Nc, q] rocBLAS GEMM
-            vals, arg = sim.max(dim=0)              # top-1 per query column
+        if fused and feats.shape[0] == 0:
+            continue
+        ci = len(index_lists)
+        index_lists.append(blob["indexes"])
+        for qs in range(0, Q, step):
+            qe = min(Q, qs + step)
+            if fused:
+                qq = query[qs:qe]
+                _, cand = ops.topk_sim(
+                    qq, feats, min(_STREAM_CANDIDATES, feats.shape[0]),
+                    precision=precision)
+                cand = cand.clamp_(min=0)
+                exact = torch.einsum("qd,qkd->qk", qq, feats[cand])
+                vals, pos = exact.max(dim=1)
+                arg = cand.gather(1, pos[:, None])[:, 0]
+            else:
+                sim = feats @ query[qs:qe].t()      # [Nc, q] rocBLAS GEMM
+                vals, arg = sim.max(dim=0)          # top-1 per query column
             upd = vals > best[qs:qe]
-            if upd.any():
-                uidx = upd.nonzero(as_tuple=True)[0]
-                best[qs:qe][uidx] = vals[uidx]
-                for j in uidx.tolist():
-                    best_key[qs + j] = idxs[int(arg[j])]
+            best[qs:qe] = torch.where(upd, vals, best[qs:qe])
+            best_row[qs:qe] = torch.where(upd, arg, best_row[qs:qe])
+            best_chunk[qs:qe] = torch.where(
+                upd, torch.full_like(arg, ci), best_chunk[qs:qe])
+    chunk_of = best_chunk.cpu().tolist()
+    row_of = best_row.cpu().tolist()
+    best_key: List[Optional[str]] = [
+        index_lists[c][r] if c >= 0 else None for c, r in zip(chunk_of, row_of)]
     return best.cpu().numpy(), best_key
 
 
@@ -92,6 +139,13 @@ def sharded_topk(query: torch.Tensor, shard: torch.Tensor, k: int = 1,
     margin. Measured on MI355X (1M x 512, 10k queries): 105.8 TF vs
     70.5 TF fp32 (1.5x) -> the DEFAULT on GPU since round 2; pass
     compute_dtype=torch.float32 to force the pure-fp32 path.
+
+    On CUDA tensors with the bf16 candidate pass and
+    min(k + rerank_margin, chunk rows) <= 16 the candidates of a chunk come
+    from the fused kernel (ops.topk_sim): the [Q, chunk] score matrix is
+    never stored, so `chunk` no longer bounds memory, and chunking does not
+    change the result. The merge across chunks and the fp32 re-rank are the
+    same. DCR_FUSED_SEARCH=0 (read per call) restores GEMM + topk.
     """
     Q = query.shape[0]
     device = query.device
@@ -102,14 +156,20 @@ def sharded_topk(query: torch.Tensor, shard: torch.Tensor, k: int = 1,
     q_mat = query.to(compute_dtype) if lowp else query
     best_v = torch.full((Q, m), -1e30, device=device)
     best_i = torch.zeros((Q, m), dtype=torch.long, device=device)
+    # fused candidate pass (ops.topk_sim): no [Q, c] score matrix
+    fused = (lowp and compute_dtype == torch.bfloat16 and query.is_cuda
+             and shard.is_cuda and Q > 0 and _fused_search_enabled())
     for s in range(0, shard.shape[0], chunk):
         block = shard[s:s + chunk]
-        if lowp:
-            sim = (q_mat @ block.t().to(compute_dtype)).float()
+        kk = min(m, block.shape[0])
+        if fused and kk <= ops.functional.TOPK_SIM_MAX_K:
+            v, i = ops.topk_sim(q_mat, block, kk, precision="bf16")
         else:
-            sim = q_mat @ block.t()                 # [Q, c] rocBLAS GEMM
-        kk = min(m, sim.shape[1])
-        v, i = sim.topk(kk, dim=1)
+            if lowp:
+                sim = (q_mat @ block.t().to(compute_dtype)).float()
+            else:
+                sim = q_mat @ block.t()             # [Q, c] rocBLAS GEMM
+            v, i = sim.topk(kk, dim=1)
         i = i + s
         cat_v = torch.cat([best_v, v], dim=1)
         cat_i = torch.cat([best_i, i], dim=1)

@@ -19,9 +19,10 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 from dcr_amd.search import stream_top1, dump_matches
+from dcr_amd.search.search import SEARCH_PRECISIONS
 
 
-def main():
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--generation_embedding", "--generation-embedding-path",
                    dest="generation_embedding", type=str, required=True,
@@ -35,7 +36,18 @@ def main():
                    type=int, default=1,
                    help="split the query matrix into this many chunks "
                         "(reference --num-chunks)")
-    args = p.parse_args()
+    p.add_argument("--search_precision", "--search-precision",
+                   dest="search_precision", type=str, default="high",
+                   choices=list(SEARCH_PRECISIONS),
+                   help="GPU candidate pass: 'high' (bf16 hi/lo split, fused "
+                        "top-k kernel + fp32 re-rank), 'bf16' (same, bf16 "
+                        "operands) or 'fp32' (plain fp32 GEMM); a CPU run "
+                        "always takes the fp32 GEMM")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     with open(args.generation_embedding, "rb") as fh:
         gen = pickle.load(fh)
@@ -47,7 +59,8 @@ def main():
         raise SystemExit(f"no embedding pickles under {root}")
     print(f"searching {query.shape[0]} queries over {len(chunk_files)} chunks")
 
-    scores, keys = stream_top1(query, chunk_files, query_chunks=args.query_chunks)
+    scores, keys = stream_top1(query, chunk_files, query_chunks=args.query_chunks,
+                               precision=args.search_precision)
     dump_matches(scores, keys, args.dump_path)
     print(f"top-1 scores: mean {scores.mean():.4f} max {scores.max():.4f} -> "
           f"{args.dump_path}")
