@@ -105,6 +105,7 @@ from .functional import (  # noqa: E402,F401
     cfg_combine,
     lincomb,
     patch_maxsim,
+    split_product,
     topk_sim,
 )
 from .adamw import FusedAdamW  # noqa: E402,F401

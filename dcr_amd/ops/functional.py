@@ -498,6 +498,70 @@ def patch_maxsim(a: torch.Tensor, b: torch.Tensor, *, precision: str = "high",
 
 
 # --------------------------------------------------------------------------
+# Split product (split-product retrieval, stype="": aligned chunks / patches)
+# --------------------------------------------------------------------------
+def split_product_operands(a: torch.Tensor, b: torch.Tensor,
+                           precision: str = "high"):
+    """(A', B') in bf16 as `split_product` hands them to the kernel: the
+    `patch_maxsim` transformation of every group's last dim, [N, G, L']."""
+    return maxsim_operands(a, b, precision)
+
+
+def _split_ref(a2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """CPU path: fp32 products of the transformed operands, max over groups.
+    One row of `a` at a time (a batched matrix-vector product over the
+    groups), so the way callers chunk the rows cannot change a bit."""
+    n = a2.shape[0]
+    bf = b2.float().transpose(0, 1)                  # [G, M, L']
+    out = torch.empty(n, b2.shape[0], dtype=torch.float32, device=a2.device)
+    for i in range(n):
+        s = torch.bmm(bf, a2[i].float().unsqueeze(2))    # [G, M, 1]
+        out[i] = s.squeeze(2).amax(dim=0)
+    return out
+
+
+def split_product(a: torch.Tensor, b: torch.Tensor, *, precision: str = "high",
+                  chunk: Optional[int] = None) -> torch.Tensor:
+    """out[n, m] = max over groups g of <a[n, g, :], b[m, g, :]>.
+
+    a [N, G, L], b [M, G, L], any float dtype and strides; returns fp32
+    [N, M]. G chunks of a flat embedding (L = D / G) or G patches of L
+    channels. On the GPU one fused kernel (dcr_amd/ops/hip/splitsim.hip)
+    contracts group by group in bf16 MFMA with fp32 accumulation and keeps
+    the running max in registers: the [N, M, G] block is never stored.
+    `precision` and `chunk` are `patch_maxsim`'s: "bf16" rounds both
+    operands, "high" (default) contracts their bf16 hi/lo split; `chunk` is
+    the number of rows of `a` per launch (bounds the transformed copy of
+    `a`) and does not change the result. CPU tensors take the same operand
+    transformation and fp32 products. A NaN group score is dropped by the
+    kernel's max unless all of an entry's groups are NaN; non-finite inputs
+    are outside the contract."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[1:] != b.shape[1:]:
+        raise ValueError("split_product: a [N, G, L] and b [M, G, L] expected, "
+                         f"got {tuple(a.shape)} and {tuple(b.shape)}")
+    if precision not in ("high", "bf16"):
+        raise ValueError(f"precision must be 'high' or 'bf16', not {precision!r}")
+    if chunk is not None and chunk < 1:
+        raise ValueError("split_product: chunk must be >= 1")
+    n, m = a.shape[0], b.shape[0]
+    if n == 0 or m == 0:
+        return torch.empty(n, m, dtype=torch.float32, device=a.device)
+    if a.shape[1] == 0 or a.shape[2] == 0:
+        raise ValueError("split_product: G and L must be >= 1")
+    step = n if chunk is None else chunk
+    b2 = _maxsim_operand(b, precision, "b")
+    run = _split_ref
+    if use_hip(a):
+        mod = require_hip("split_product")
+        if mod is not None:  # None: debug fallback on GPU
+            count_dispatch('split_product')
+            run = mod.split_product
+    outs = [run(_maxsim_operand(a[i:i + step], precision, "a"), b2)
+            for i in range(0, n, step)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+
+# --------------------------------------------------------------------------
 # Top-k similarity search (embedding search)
 # --------------------------------------------------------------------------
 TOPK_SIM_MAX_K = 16   # list capacity of the fused kernel

@@ -945,6 +945,49 @@ at::Tensor patch_maxsim(at::Tensor A, at::Tensor B) {
   return out;
 }
 
+// ---------------------------------------------------------------- splitsim
+// out[n, m] = max over groups g of <A[n, g, :], B[m, g, :]>, fp32. One fused
+// launch: the [N, M, G] block of per-group scores is never stored. splits =
+// 0 takes the launcher's rule; any value gives the same bits.
+at::Tensor split_product(at::Tensor A, at::Tensor B, int64_t splits) {
+  TORCH_CHECK(A.is_cuda() && B.is_cuda() && A.device() == B.device(),
+              "split_product: CUDA tensors on one device expected");
+  TORCH_CHECK(A.scalar_type() == at::kBFloat16 &&
+              B.scalar_type() == at::kBFloat16, "split_product: bf16 only");
+  TORCH_CHECK(A.dim() == 3 && B.dim() == 3,
+              "split_product: A [N, G, L] and B [M, G, L] expected");
+  TORCH_CHECK(A.is_contiguous() && B.is_contiguous(),
+              "split_product: contiguous operands expected");
+  const int64_t N = A.size(0), G = A.size(1), L = A.size(2);
+  const int64_t M = B.size(0);
+  TORCH_CHECK(B.size(1) == G, "split_product: G mismatch");
+  TORCH_CHECK(B.size(2) == L, "split_product: L mismatch");
+  TORCH_CHECK(L >= 8 && L % 8 == 0, "split_product: L % 8 != 0");
+  TORCH_CHECK(G >= 1, "split_product: G >= 1 expected");
+  TORCH_CHECK(G < (1LL << 30) && L < (1LL << 30) && G * L < (1LL << 31),
+              "split_product: G * L must stay below 2^31");
+  TORCH_CHECK(N < (1LL << 31) && M < (1LL << 31),
+              "split_product: N and M must stay below 2^31");
+  TORCH_CHECK(splits >= 0 && splits <= G,
+              "split_product: 0 <= splits <= G expected");
+  const auto opts = A.options().dtype(at::kFloat);
+  if (N == 0 || M == 0) return at::empty({N, M}, opts);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(A.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(B.data_ptr()) % 16 == 0,
+              "split_product: operands must be 16-byte aligned");
+  const int S = split_product_splits(N, M, (int)G, (int)splits);
+  const int64_t tiles = ((N + 127) / 128) * ((M + 127) / 128);
+  TORCH_CHECK(tiles * S < (1LL << 31),
+              "split_product: too many blocks for one launch; pass fewer "
+              "rows of A per call");
+  auto out = S > 1
+      ? at::full({N, M}, -std::numeric_limits<float>::infinity(), opts)
+      : at::empty({N, M}, opts);
+  split_product_launch(A.data_ptr(), B.data_ptr(), out.data_ptr<float>(), N, M,
+                       (int)G, (int)L, S, cur_stream());
+  return out;
+}
+
 // ---------------------------------------------------------------- topk_sim
 // Per row of q [Nq, D] the m best (score, column) pairs of q x^T over
 // x [Nx, D], higher score first and the lower column first among equals:
@@ -998,6 +1041,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("m"), pybind11::arg("stripes") = 0);
   mod.def("gemm_bf16", &gemm_bf16);
   mod.def("patch_maxsim", &patch_maxsim);
+  mod.def("split_product", &split_product, pybind11::arg("A"),
+          pybind11::arg("B"), pybind11::arg("splits") = 0);
   mod.def("linear_wgrad", &linear_wgrad, pybind11::arg("dy2d"),
           pybind11::arg("x2d"), pybind11::arg("want_db"),
           pybind11::arg("split") = 0, pybind11::arg("tile") = 0);

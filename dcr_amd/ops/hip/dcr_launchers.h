@@ -174,6 +174,16 @@ void linear_wgrad_launch(const void* dy, const void* x, float* slab,
 void patch_maxsim_launch(const void* A, const void* B, float* out, long N,
                          long M, int P, int Q, int K, hipStream_t st);
 
+// splitsim.hip — out[n,m] = max_g <A[n,g,:], B[m,g,:]>; A [N,G,L] and
+// B [M,G,L] bf16 contiguous, L % 8 == 0, G*L < 2^31; out [N,M] fp32.
+// S = split_product_splits(N, M, G, splits_req) blocks share a tile's groups
+// (splits_req > 0 forces the count, clamped to G). S == 1: plain stores, out
+// may be uninitialised. S > 1: out pre-filled with -inf, partial maxima are
+// combined with atomics. N, M, G >= 1; ceil(N/128)*ceil(M/128)*S < 2^31.
+int split_product_splits(long N, long M, int G, int splits_req);
+void split_product_launch(const void* A, const void* B, float* out, long N,
+                          long M, int G, int L, int S, hipStream_t st);
+
 // topk_sim.hip — per row of Qm [Nq,K] the m best (score, column) pairs of
 // Qm X^T over X [Nx,K]; bf16 contiguous, K % 8 == 0, 1 <= m <= 16, m <= Nx,
 // Nx < 2^31. topk_sim_plan gives the list capacity (1/4/8/16 >= m), the

@@ -34,19 +34,10 @@
 
 namespace dcr_maxsim {
 
-using namespace dcr_stage;  // staging types, geometry, stage_load/stage_store
+using namespace dcr_stage;  // staging types, geometry, stage_load/stage_store,
+                            // atomic_max_f32
 
 constexpr int GROUP = 16;               // A-tiles per block-order group
-
-// out = max(out, v) for floats through integer atomics. Non-negative floats
-// order like signed ints and beat every bit pattern with the sign set;
-// negative floats order inversely to their unsigned patterns, which are all
-// above the non-negative ones. -0.0 takes the unsigned path, +0.0 the signed.
-__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-  const int bits = __float_as_int(v);
-  if (bits >= 0) atomicMax(reinterpret_cast<int*>(addr), bits);
-  else atomicMin(reinterpret_cast<unsigned*>(addr), (unsigned)bits);
-}
 
 __global__ __launch_bounds__(256)
 void patch_maxsim_kernel(const bf16_t* __restrict__ A,

@@ -9,6 +9,7 @@ BASELINE-sanctioned library path; everything runs on CPU too (config 1).
 from __future__ import annotations
 
 import io
+import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -43,14 +44,22 @@ def einsum_in_chunks(feat_a: torch.Tensor, feat_b: torch.Tensor,
     splitloss path (diff_retrieval.py:397-400): same-patch dot, max over
     patches.
 
-    stype='cross' on CUDA tensors runs the fused HIP kernel
-    (dcr_amd.ops.patch_maxsim), which never builds the [chunk, M, P, Q]
-    block; `precision` ('high' or 'bf16') is that op's and has no effect
-    on any other path."""
-    if stype == "cross" and feat_a.is_cuda and feat_b.is_cuda:
-        from ..ops import patch_maxsim
-        return patch_maxsim(feat_a.transpose(1, 2), feat_b.transpose(1, 2),
-                            precision=precision, chunk=max(1, chunk))
+    CUDA tensors run the fused HIP kernels: stype='cross'
+    dcr_amd.ops.patch_maxsim, which never builds the [chunk, M, P, Q]
+    block, and stype='' dcr_amd.ops.split_product, which never builds the
+    [chunk, M, P] block (DCR_FUSED_SPLITSIM=0, read per call, restores the
+    einsum for stype=''). `precision` ('high' or 'bf16') is those ops' and
+    has no effect on the einsum paths."""
+    if feat_a.is_cuda and feat_b.is_cuda:
+        if stype == "cross":
+            from ..ops import patch_maxsim
+            return patch_maxsim(feat_a.transpose(1, 2), feat_b.transpose(1, 2),
+                                precision=precision, chunk=max(1, chunk))
+        if os.environ.get("DCR_FUSED_SPLITSIM", "1") != "0":
+            from ..ops import split_product
+            return split_product(feat_a.transpose(1, 2),
+                                 feat_b.transpose(1, 2),
+                                 precision=precision, chunk=max(1, chunk))
     sims = []
     for i in range(0, feat_a.shape[0], chunk):
         a = feat_a[i:i + chunk].float()

@@ -53,11 +53,15 @@ def parse_args():
     p.add_argument("--pretrained", default="", type=str)
     p.add_argument("--similarity_metric", default="dotproduct", type=str)
     p.add_argument("--num_loss_chunks", default=1, type=int,
-                   help="(reference flag; splitloss here derives per-patch "
-                        "descriptors from the model's own token/spatial map "
-                        "instead of slicing the flat embedding)")
+                   help="splitloss with --stype '': c > 1 slices the flat "
+                        "L2-normalised embedding [N, D] into c chunks of "
+                        "D / c (the reference's form: dot product of aligned "
+                        "chunks, max over chunks; D %% c must be 0). 1 "
+                        "(default) takes per-patch descriptors from the "
+                        "model's own token/spatial map instead")
     p.add_argument("--numpatches", default=1, type=int,
-                   help="(reference flag; see --num_loss_chunks)")
+                   help="reference flag: a value > 1 overrides "
+                        "--num_loss_chunks")
     p.add_argument("--isvit", action="store_true",
                    help="(reference flag; ViT-ness is detected from the model)")
     p.add_argument("--layer", default=1, type=int)
@@ -68,10 +72,11 @@ def parse_args():
     p.add_argument("--einsum_chunks", default=30, type=int)
     p.add_argument("--maxsim_precision", default="high",
                    choices=["high", "bf16"],
-                   help="splitloss with --stype cross on a GPU (fused patch "
-                        "max-similarity kernel): 'high' contracts a bf16 "
-                        "hi/lo split of the features (fp32-grade scores, 3x "
-                        "the FLOPs), 'bf16' rounds them to bf16")
+                   help="splitloss on a GPU, either --stype (fused patch "
+                        "max-similarity / split-product kernels), and the "
+                        "--num_loss_chunks form anywhere: 'high' contracts a "
+                        "bf16 hi/lo split of the features (fp32-grade scores, "
+                        "3x the FLOPs), 'bf16' rounds them to bf16")
     p.add_argument("--dontsave", action="store_true")
     p.add_argument("--num_matches", default=4, type=int)
     p.add_argument("--imsize", default=224, type=int)
@@ -121,12 +126,12 @@ def build_backbone(args, device):
 @torch.no_grad()
 def _patch_features(model, loader, device, args):
     """[N, D, P] L2-normalized per-patch descriptors: ViT token features
-    (get_intermediate_layers) or the CNN's final spatial map. They go to
-    the CPU, except for --stype cross on a GPU: the fused max-similarity
-    kernel takes them on the device (bf16 under --maxsim_precision bf16,
-    else fp32)."""
+    (get_intermediate_layers) or the CNN's final spatial map. On a GPU they
+    stay on the device, where the fused max-similarity (--stype cross) and
+    split-product (--stype '') kernels take them (bf16 under
+    --maxsim_precision bf16, else fp32)."""
     import torch.nn.functional as F_
-    on_device = args.stype == "cross" and device.type == "cuda"
+    on_device = device.type == "cuda"
     keep_dtype = torch.bfloat16 if args.maxsim_precision == "bf16" \
         else torch.float32
     feats = []
@@ -143,6 +148,23 @@ def _patch_features(model, loader, device, args):
         f = F_.normalize(f, dim=1)
         feats.append(f.to(keep_dtype) if on_device else f.cpu())
     return torch.cat(feats)
+
+
+def chunked_embedding_similarity(feat_a, feat_b, c, precision="high",
+                                 chunk=None):
+    """The reference's splitloss (diff_retrieval.py:394-400) on flat
+    L2-normalised embeddings [N, D] and [M, D]: each is viewed as c chunks
+    of D / c, out[n, m] = max over chunks of the aligned chunks' dot product
+    (dcr_amd.ops.split_product: the fused HIP kernel on CUDA tensors)."""
+    from dcr_amd.ops import split_product
+    d = feat_a.shape[1]
+    if d % c:
+        raise ValueError(f"splitloss: the embedding width {d} is not "
+                         f"divisible by {c} chunks (--num_loss_chunks / "
+                         "--numpatches)")
+    return split_product(feat_a.reshape(feat_a.shape[0], c, d // c),
+                         feat_b.reshape(feat_b.shape[0], c, d // c),
+                         precision=precision, chunk=chunk)
 
 
 def main():
@@ -191,7 +213,18 @@ def main():
     val_f = l2_normalize(val_f)
 
     # HOT LOOP 2: similarity
-    if args.similarity_metric == "splitloss":
+    n_chunks = args.numpatches if args.numpatches > 1 else args.num_loss_chunks
+    if args.similarity_metric == "splitloss" and args.stype == "" \
+            and n_chunks > 1:
+        # the reference's form (:394-400): aligned chunks of the flat
+        # embedding, max over chunks; no second extraction pass
+        sim = chunked_embedding_similarity(
+            query_f, val_f, n_chunks, precision=args.maxsim_precision,
+            chunk=max(1, len(query_ds) // max(1, args.einsum_chunks)))
+        sim_tt = chunked_embedding_similarity(
+            val_f, val_f, n_chunks, precision=args.maxsim_precision,
+            chunk=max(1, len(val_ds) // max(1, args.einsum_chunks)))
+    elif args.similarity_metric == "splitloss":
         # patch-wise max similarity (reference :393-400, einsum :643-662):
         # features here are [N, D, P] per-patch descriptors
         qp_ = _patch_features(model, loader(query_ds), device, args)
