@@ -6,13 +6,21 @@ weight_decay 1e-2). Instead of ~700 per-tensor kernel launches per step,
 this optimizer re-parameterizes the model so that
 
 * every parameter tensor is a VIEW into one contiguous flat buffer,
-* gradients land in one contiguous flat arena via batched
-  ``gather_grads()`` (autograd owns per-param grads; no per-param adds),
+* gradients land in one contiguous flat arena via ``gather_grads()``
+  (autograd owns per-param grads; no per-param adds): on the GPU one
+  ``grad_gather_kernel`` launch copies the whole list and takes its sum of
+  squares on the way (ops/hip/grad_tail.hip); accumulation micro-steps and
+  gradients whose layout differs from their arena view go through batched
+  ``_foreach`` kernels / ``copy_``,
 * Adam state (m, v) are two more flat buffers,
 
 so one step is ONE elementwise HIP kernel over four flat arrays —
 HBM-bound by design (~8 TB/s on MI355X), and the flat grad buffer doubles
 as the bucket arena for RCCL all-reduce (dcr_amd/parallel/ddp.py).
+``clip_and_step()`` is the training step's tail: the global-norm clip
+coefficient stays on the device and the AdamW kernel applies it, so the
+host never waits for the norm. ``DCR_FUSED_GRAD_TAIL=0`` (read per call)
+restores the ``_foreach_copy_`` / ``vector_norm`` / host-compare path.
 
 Flatten AFTER moving the model to its device; ``p.data`` is replaced by
 buffer views.
@@ -38,16 +46,26 @@ and requantises; rounding is to nearest even, deterministic.
 """
 from __future__ import annotations
 
+import os
 from typing import Iterable, List, Tuple
 
 import torch
 
 from . import use_hip, require_hip, count_dispatch
 
+# grad_gather_kernel's virtual block: elements of one parameter per block,
+# and the grid (0: min(virtual blocks, 8192)). Sweep: ops/hip/README.md.
+GATHER_CH = 16384
+GATHER_GRID = 0
+
 QBLOCK = 256
 FP8_MAX = 448.0
 STATE_FORMAT = {"state_bits": 8, "qblock": QBLOCK, "codec": "e4m3fn_absmax",
                 "second_moment": "sqrt"}
+
+
+def fused_grad_tail_enabled() -> bool:
+    return os.environ.get("DCR_FUSED_GRAD_TAIL", "1") != "0"
 
 
 def _nblocks(numel: int) -> int:
@@ -199,6 +217,16 @@ class FusedAdamW:
         if self.master is not None:
             self.master.copy_(self.flat_param.float())
 
+        # native gradient tail (ops/hip/grad_tail.hip): per-virtual-block
+        # sums of squares, the {sumsq, norm, coef} device record, and
+        # whether `_partials` currently holds the sums of what is in the
+        # arena (see arena_written())
+        self._nvb_all = sum((p.numel() + GATHER_CH - 1) // GATHER_CH
+                            for p in self.params)
+        self._partials = None
+        self._norm_rec = None
+        self._sumsq_valid = False
+
         # device-state mode (round-2 draft, DCR_DEV_ADAMW=1): all per-step
         # scalars live in hyper[8] on device so the whole optimizer tail is
         # hipGraph-capturable — see elementwise.hip adamw_dev section.
@@ -216,6 +244,7 @@ class FusedAdamW:
         # is a copy, so the zero is skippable (1.7 GB write saved).
         # _ensure_cold_slices() covers the rare dynamic-graph case where
         # a later cycle leaves some params ungathered.
+        self.arena_written()
         if len(self._gathered) != len(self.params):
             self.flat_grad.zero_()
             self._skipped_zero = False
@@ -236,16 +265,58 @@ class FusedAdamW:
         stale = [self._view_of[id(p)] for p in self.params
                  if id(p) not in self._gathered]
         if stale:
+            self.arena_written()
             torch._foreach_zero_(stale)
         self._skipped_zero = False
 
+    def arena_written(self):
+        """Declare that ``flat_grad`` holds, or is about to hold, values the
+        fused sum of squares did not see. EVERY site that writes the arena
+        outside ``grad_gather_kernel``'s own full-coverage copy calls this:
+        add-mode and partial gathers, the per-parameter fallback copy,
+        ``_ensure_cold_slices``' zeroing, ``zero_grad``, the clip's ``mul_``
+        and the clipped store-back of the AdamW kernel, and outside this
+        class the bucket all-reduce and ``div_`` of
+        ``GradBucketAllReduce`` and the fp16 scaler's ``mul_`` in
+        ``Trainer.train_step``. A new writer of the arena must call it too:
+        ``clip_and_step`` then takes the standalone sum-of-squares pass
+        instead of trusting a sum of values that are no longer there."""
+        self._sumsq_valid = False
+
+    def _native_tail(self):
+        """The extension when the native gather / norm / clip path applies to
+        this call, else None (CPU, switch off, or stream capture: a captured
+        copy of the pinned pointer table would replay stale pointers)."""
+        if not self.flat_grad.is_cuda or not fused_grad_tail_enabled():
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        return require_hip("grad_tail")
+
+    def _get_partials(self) -> torch.Tensor:
+        if self._partials is None:
+            self._partials = torch.empty(
+                max(self._nvb_all, 1), dtype=torch.float32,
+                device=self.flat_grad.device)
+        return self._partials
+
     @torch.no_grad()
-    def gather_grads(self, params=None):
-        """Move autograd-produced p.grad tensors into the flat arena with
-        batched _foreach kernels (first gather per param after zero_grad
-        is a copy over the zeroed slice; later gathers — gradient
-        accumulation micro-steps — add). Called per-bucket by the DDP
-        engine (before each bucket's all-reduce) and by finalize()."""
+    def gather_grads(self, params=None, sumsq: bool = True):
+        """Move autograd-produced p.grad tensors into the flat arena (first
+        gather per param after zero_grad is a copy over the slice; later
+        gathers — gradient accumulation micro-steps — add). Called
+        per-bucket by the DDP engine (before each bucket's all-reduce,
+        with ``sumsq=False``: the all-reduce changes the values) and by
+        finalize().
+
+        On the GPU the copies are one ``grad_gather_kernel`` launch; a
+        gradient whose dtype or memory layout differs from its arena view
+        is copied with ``copy_``. When one call copies EVERY parameter that
+        way and ``sumsq`` is on, the kernel also leaves the arena's sum of
+        squares in ``_partials`` and the validity flag is set. Adds use
+        ``_foreach_add_``; without the native path (CPU, switch off, stream
+        capture) the copies use ``_foreach_copy_``."""
+        m = self._native_tail()
         copy_d, copy_s, add_d, add_s = [], [], [], []
         for p in (params if params is not None else self.params):
             g = p.grad
@@ -262,7 +333,23 @@ class FusedAdamW:
                 copy_s.append(g)
                 self._gathered.add(id(p))
             p.grad = None
-        if copy_d:
+        if copy_d or add_d:
+            self.arena_written()
+        if copy_d and m is not None:
+            fused = (sumsq and params is None and not add_d
+                     and len(copy_d) == len(self.params))
+            rejected = m.grad_gather(
+                self.flat_grad, copy_d, copy_s,
+                self._get_partials() if fused else None,
+                GATHER_CH, GATHER_GRID)
+            count_dispatch('grad_gather')
+            for i in rejected:
+                count_dispatch('grad_gather_fallback')
+                copy_d[i].copy_(copy_s[i])
+            self._sumsq_valid = fused and not rejected
+        elif copy_d:
+            if self.flat_grad.is_cuda:
+                count_dispatch('grad_gather_foreach')
             torch._foreach_copy_(copy_d, copy_s)
         if add_d:
             torch._foreach_add_(add_d, add_s)
@@ -389,14 +476,81 @@ class FusedAdamW:
         """Global L2 grad clip (reference: diff_train.py:657-663, max 1.0).
         fp32 accumulation via the dtype arg — `.float()` would
         materialize a full fp32 copy of the 1.7 GB bf16 arena first
-        (~1 ms/step, profile_aten r02c8)."""
+        (~1 ms/step, profile_aten r02c8).
+
+        This call always takes aten's norm over the arena and reads it on
+        the host, also right after a gather that left a valid fused sum of
+        squares: a caller of ``clip_grad_norm_`` + ``step`` pays for the norm
+        a second time. The training step uses ``clip_and_step``."""
         self.gather_grads()  # no-op when finalize() already ran
         self._ensure_cold_slices()
+        if self.flat_grad.is_cuda:
+            count_dispatch('grad_norm_aten')
         norm = torch.linalg.vector_norm(self.flat_grad, dtype=torch.float32)
         scale = max_norm / (norm + 1e-6)
         if float(norm) > max_norm:
+            self.arena_written()
             self.flat_grad.mul_(scale.to(self.flat_grad.dtype))
         return norm
+
+    def _norm_record(self, m, max_norm: float) -> torch.Tensor:
+        """Device record {sumsq, norm, coef} of the arena as it stands: from
+        the gather's fused partials when they are valid, else from the
+        standalone pass over the same virtual-block partition (same bits)."""
+        if self._norm_rec is None:
+            self._norm_rec = torch.zeros(3, dtype=torch.float32,
+                                         device=self.flat_grad.device)
+        partials = self._get_partials()
+        if not self._sumsq_valid:
+            count_dispatch('grad_sumsq')
+            m.grad_sumsq(self.flat_grad, self._grad_views, partials,
+                         GATHER_CH, GATHER_GRID)
+            self._sumsq_valid = True
+        count_dispatch('grad_norm_finalize')
+        m.sumsq_finalize(partials, self._nvb_all, float(max_norm),
+                         self._norm_rec)
+        return self._norm_rec
+
+    @torch.no_grad()
+    def clip_and_step(self, max_norm: float, lr: float | None = None) -> torch.Tensor:
+        """``clip_grad_norm_(max_norm)`` followed by ``step(lr)`` with no
+        host read in between: the norm and the clip coefficient stay in a
+        device record, and the AdamW kernel applies the coefficient, storing
+        the clipped gradient back into the arena when it is not 1, so the
+        arena, parameters, master copy and moments end as the two calls
+        leave them. Returns the gradient norm as a 0-dim device tensor (a
+        view of the record: the next call overwrites it). CPU, 8-bit state,
+        ``DCR_FUSED_GRAD_TAIL=0`` and stream capture take the two calls.
+
+        ``max_norm`` means what it means to ``clip_grad_norm_``, on every
+        path: the gradient is scaled whenever ``norm > max_norm``, so
+        ``max_norm = 0`` does NOT switch clipping off, it zeroes the
+        gradient, and a negative ``max_norm`` flips its sign."""
+        m = self._native_tail() if self.state_bits == 32 else None
+        if m is None:
+            norm = self.clip_grad_norm_(max_norm)
+            self.step(lr=lr)
+            return norm
+        self.gather_grads()  # no-op when finalize() already ran
+        self._ensure_cold_slices()
+        rec = self._norm_record(m, max_norm)
+        if lr is not None:
+            self.lr = lr
+        self.step_count += 1
+        count_dispatch('adamw')
+        count_dispatch('adamw_clip')
+        if self.master is not None:
+            m.adamw_step_bf16_clip(
+                self.flat_param, self.flat_grad, self.master, self.exp_avg,
+                self.exp_avg_sq, self.lr, self.beta1, self.beta2, self.eps,
+                self.weight_decay, self.step_count, rec)
+        else:
+            m.adamw_step_clip(
+                self.flat_param, self.flat_grad, self.exp_avg,
+                self.exp_avg_sq, self.lr, self.beta1, self.beta2, self.eps,
+                self.weight_decay, self.step_count, rec)
+        self.arena_written()  # the kernel stores the clipped gradient back
+        return rec[1]
 
     # -- checkpointing -----------------------------------------------------
     def state_dict(self):

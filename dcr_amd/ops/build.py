@@ -28,6 +28,7 @@ SOURCES = [
     HIP_DIR / "conv_nhwc.hip",
     HIP_DIR / "conv_nhwc_bwd.hip",
     HIP_DIR / "gemm.hip",
+    HIP_DIR / "grad_tail.hip",
     HIP_DIR / "maxsim.hip",
     HIP_DIR / "splitsim.hip",
     HIP_DIR / "topk_sim.hip",

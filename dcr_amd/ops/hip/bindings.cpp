@@ -8,7 +8,9 @@
 
 #include <climits>
 #include <cstdint>
+#include <cstring>
 #include <limits>
+#include <vector>
 
 #include "dcr_launchers.h"
 
@@ -298,6 +300,189 @@ void adamw_step_bf16(at::Tensor p, at::Tensor g, at::Tensor master,
                     m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
                     (float)lr, (float)beta1, (float)beta2, (float)eps,
                     (float)wd, step, cur_stream());
+}
+
+// ---------------------------------------------------------------- grad tail
+// grad_tail.hip: one-launch gradient gather with a fused sum of squares, the
+// finalize that turns it into {sumsq, norm, coef}, and the AdamW kernels
+// that read coef from that record.
+namespace {
+
+void gt_check_arena(const at::Tensor& arena, int64_t ch) {
+  TORCH_CHECK(arena.is_cuda() && arena.dim() == 1 && arena.is_contiguous(),
+              "grad tail: the arena must be a flat contiguous GPU tensor");
+  TORCH_CHECK(arena.scalar_type() == at::kBFloat16 ||
+              arena.scalar_type() == at::kFloat,
+              "grad tail: bf16 or fp32 arena expected");
+  TORCH_CHECK(ch >= 8 && ch % 8 == 0 && ch <= (1 << 24),
+              "grad tail: chunk must be a multiple of 8 elements, got ", ch);
+}
+
+// element offset of an arena view; checks that it lies inside the arena
+int64_t gt_view_offset(const at::Tensor& arena, const at::Tensor& view) {
+  TORCH_CHECK(view.scalar_type() == arena.scalar_type() &&
+              view.device() == arena.device() &&
+              view.is_non_overlapping_and_dense(),
+              "grad tail: not a dense view of the arena");
+  const int64_t es = arena.element_size();
+  const int64_t byte_off = (const char*)view.data_ptr() - (const char*)arena.data_ptr();
+  TORCH_CHECK(byte_off >= 0 && byte_off % es == 0 &&
+              byte_off / es + view.numel() <= arena.numel(),
+              "grad tail: view outside the arena");
+  return byte_off / es;
+}
+
+// raw copy is right when both hold the same elements in the same memory
+// order: same dtype, dense, equal strides on every dimension of size > 1
+// (a [K,C,1,1] weight is contiguous in both memory formats and may carry
+// either stride tuple)
+bool gt_qualifies(const at::Tensor& g, const at::Tensor& view) {
+  if (!g.defined() || g.device() != view.device() ||
+      g.scalar_type() != view.scalar_type() || g.sizes() != view.sizes() ||
+      !g.is_non_overlapping_and_dense())
+    return false;
+  for (int64_t d = 0; d < g.dim(); ++d)
+    if (g.size(d) > 1 && g.stride(d) != view.stride(d)) return false;
+  return reinterpret_cast<uintptr_t>(g.data_ptr()) % g.element_size() == 0;
+}
+
+// rows of {source address, destination offset, count, block prefix}: filled
+// into pinned memory and sent with one non-blocking copy, so the caching
+// host allocator keeps the block from reuse until the copy has run
+at::Tensor gt_upload(const at::Tensor& arena, const std::vector<int64_t>& rows) {
+  auto host = at::empty({(int64_t)rows.size()},
+                        at::TensorOptions().dtype(at::kLong).pinned_memory(true));
+  std::memcpy(host.data_ptr<int64_t>(), rows.data(), rows.size() * sizeof(int64_t));
+  auto dev = at::empty({(int64_t)rows.size()}, arena.options().dtype(at::kLong));
+  dev.copy_(host, /*non_blocking=*/true);
+  return dev;
+}
+
+float* gt_partials(const c10::optional<at::Tensor>& partials,
+                   const at::Tensor& arena, int64_t nvb) {
+  if (!partials.has_value()) return nullptr;
+  TORCH_CHECK(partials->is_cuda() && partials->device() == arena.device() &&
+              partials->scalar_type() == at::kFloat &&
+              partials->is_contiguous() && partials->numel() >= nvb,
+              "grad tail: partials must hold ", nvb, " floats on the GPU");
+  return partials->data_ptr<float>();
+}
+
+}  // namespace
+
+// Copies every qualifying grads[i] into views[i] (views of `arena`) in one
+// launch; with `partials` also writes each virtual block's sum of squares.
+// Returns the indices that did not qualify: the caller copies those.
+std::vector<int64_t> grad_gather(at::Tensor arena, std::vector<at::Tensor> views,
+                                 std::vector<at::Tensor> grads,
+                                 c10::optional<at::Tensor> partials,
+                                 int64_t ch, int64_t grid) {
+  gt_check_arena(arena, ch);
+  TORCH_CHECK(views.size() == grads.size(), "grad_gather: list lengths differ");
+  std::vector<int64_t> rows, rejected;
+  rows.reserve(4 * views.size());
+  int64_t nvb = 0;
+  for (size_t i = 0; i < views.size(); ++i) {
+    if (!gt_qualifies(grads[i], views[i])) {
+      rejected.push_back((int64_t)i);
+      continue;
+    }
+    const int64_t n = views[i].numel();
+    if (n == 0) continue;
+    const int64_t off = gt_view_offset(arena, views[i]);
+    rows.push_back((int64_t)reinterpret_cast<uintptr_t>(grads[i].data_ptr()));
+    rows.push_back(off);
+    rows.push_back(n);
+    rows.push_back(nvb);
+    nvb += (n + ch - 1) / ch;
+  }
+  if (rows.empty()) return rejected;
+  float* pp = gt_partials(partials, arena, nvb);
+  auto table = gt_upload(arena, rows);
+  grad_gather_launch(dtype_of(arena), (const long*)table.data_ptr<int64_t>(),
+                     (int)(rows.size() / 4), nvb, arena.data_ptr(), pp, (int)ch,
+                     grad_gather_grid(nvb, (int)grid), /*store=*/true,
+                     cur_stream());
+  return rejected;
+}
+
+// Standalone sum of squares of the arena slices `views`, over the same
+// virtual-block partition grad_gather uses for the same list: same bits.
+// Returns the number of partials written.
+int64_t grad_sumsq(at::Tensor arena, std::vector<at::Tensor> views,
+                   at::Tensor partials, int64_t ch, int64_t grid) {
+  gt_check_arena(arena, ch);
+  std::vector<int64_t> rows;
+  rows.reserve(4 * views.size());
+  int64_t nvb = 0;
+  for (const auto& v : views) {
+    const int64_t n = v.numel();
+    if (n == 0) continue;
+    const int64_t off = gt_view_offset(arena, v);
+    rows.push_back((int64_t)reinterpret_cast<uintptr_t>(
+        (const char*)arena.data_ptr() + off * arena.element_size()));
+    rows.push_back(off);
+    rows.push_back(n);
+    rows.push_back(nvb);
+    nvb += (n + ch - 1) / ch;
+  }
+  float* pp = gt_partials(partials, arena, nvb);
+  if (rows.empty()) return 0;
+  auto table = gt_upload(arena, rows);
+  grad_gather_launch(dtype_of(arena), (const long*)table.data_ptr<int64_t>(),
+                     (int)(rows.size() / 4), nvb, arena.data_ptr(), pp, (int)ch,
+                     grad_gather_grid(nvb, (int)grid), /*store=*/false,
+                     cur_stream());
+  return nvb;
+}
+
+// partials[0:nvb] -> rec = {sumsq, norm, coef} (float[3] on the GPU)
+void sumsq_finalize(at::Tensor partials, int64_t nvb, double max_norm,
+                    at::Tensor rec) {
+  TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat &&
+              partials.is_contiguous() && nvb >= 0 && partials.numel() >= nvb,
+              "sumsq_finalize: partials must hold nvb floats on the GPU");
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kFloat &&
+              rec.is_contiguous() && rec.numel() == 3,
+              "sumsq_finalize: rec must be float[3] on the GPU");
+  sumsq_finalize_launch(partials.data_ptr<float>(), nvb, (float)max_norm,
+                        rec.data_ptr<float>(), cur_stream());
+}
+
+static void gt_check_rec(const at::Tensor& rec, const at::Tensor& p) {
+  TORCH_CHECK(rec.is_cuda() && rec.device() == p.device() &&
+              rec.scalar_type() == at::kFloat && rec.is_contiguous() &&
+              rec.numel() == 3, "adamw_clip: rec must be float[3] on the GPU");
+}
+
+void adamw_step_clip(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+                     double lr, double beta1, double beta2, double eps,
+                     double wd, int64_t step, at::Tensor rec) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat &&
+              g.scalar_type() == at::kFloat && g.numel() == p.numel(),
+              "adamw_clip: fp32 flat params and grads expected");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() &&
+              v.is_contiguous());
+  gt_check_rec(rec, p);
+  adamw_clip_launch(p.data_ptr<float>(), g.data_ptr<float>(),
+                    m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
+                    (float)lr, (float)beta1, (float)beta2, (float)eps,
+                    (float)wd, step, rec.data_ptr<float>(), cur_stream());
+}
+
+void adamw_step_bf16_clip(at::Tensor p, at::Tensor g, at::Tensor master,
+                          at::Tensor m, at::Tensor v, double lr, double beta1,
+                          double beta2, double eps, double wd, int64_t step,
+                          at::Tensor rec) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kBFloat16 &&
+              g.scalar_type() == at::kBFloat16 && g.numel() == p.numel());
+  TORCH_CHECK(master.scalar_type() == at::kFloat);
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && master.is_contiguous());
+  gt_check_rec(rec, p);
+  adamw_bf16_clip_launch(p.data_ptr(), g.data_ptr(), master.data_ptr<float>(),
+                         m.data_ptr<float>(), v.data_ptr<float>(), p.numel(),
+                         (float)lr, (float)beta1, (float)beta2, (float)eps,
+                         (float)wd, step, rec.data_ptr<float>(), cur_stream());
 }
 
 // device-state AdamW (round-2 draft): hyper = float[8] cuda tensor
@@ -1079,6 +1264,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adamw_step", &adamw_step);
   mod.def("adamw_step_bf16", &adamw_step_bf16);
   mod.def("adamw_step_dev", &adamw_step_dev);
+  mod.def("adamw_step_clip", &adamw_step_clip);
+  mod.def("adamw_step_bf16_clip", &adamw_step_bf16_clip);
+  mod.def("grad_gather", &grad_gather, py::arg("arena"), py::arg("views"),
+          py::arg("grads"), py::arg("partials") = py::none(),
+          py::arg("ch") = 16384, py::arg("grid") = 0);
+  mod.def("grad_sumsq", &grad_sumsq, py::arg("arena"), py::arg("views"),
+          py::arg("partials"), py::arg("ch") = 16384, py::arg("grid") = 0);
+  mod.def("sumsq_finalize", &sumsq_finalize);
   mod.def("adamw8_step", &adamw8_step, py::arg("p"), py::arg("g"),
           py::arg("exp_avg_q"), py::arg("exp_avg_absmax"),
           py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_absmax"), py::arg("lr"),

@@ -68,6 +68,28 @@ void adamw_launch(float* p, const float* g, float* m, float* v, long n,
 void adamw_bf16_launch(void* p, const void* g, float* master, float* m,
                        float* v, long n, float lr, float b1, float b2,
                        float eps, float wd, long step, hipStream_t s);
+// clip-aware AdamW: rec = device float[3] {sumsq, norm, coef} written by
+// sumsq_finalize_launch; when coef != 1 the clipped gradient is stored back
+// into g and used for the update
+void adamw_clip_launch(float* p, float* g, float* m, float* v, long n,
+                       float lr, float b1, float b2, float eps, float wd,
+                       long step, const float* rec, hipStream_t s);
+void adamw_bf16_clip_launch(void* p, void* g, float* master, float* m,
+                            float* v, long n, float lr, float b1, float b2,
+                            float eps, float wd, long step, const float* rec,
+                            hipStream_t s);
+// grad_tail.hip — dt is DT_BF16 or DT_F32. table: device int64 [nparams, 4]
+// = {source address, destination element offset in arena, element count,
+// virtual blocks before this parameter}; a virtual block is `ch` elements
+// of one parameter (ch % 8 == 0), nvb their total. store: copy source to
+// arena; partials (nvb floats, uninitialised; may be null when store) gets
+// each virtual block's sum of squares. !store needs partials and only reads.
+int grad_gather_grid(long nvb, int grid_req);
+void grad_gather_launch(DType dt, const long* table, int nparams, long nvb,
+                        void* arena, float* partials, int ch, int grid,
+                        bool store, hipStream_t s);
+void sumsq_finalize_launch(const float* partials, long nvb, float max_norm,
+                           float* rec, hipStream_t s);
 // device-state AdamW (round-2 draft; hipGraph-capturable step)
 void adamw_dev_launch(int bf16, void* p, const void* g, float* master,
                       float* m, float* v, long n, float b1, float b2,

@@ -54,10 +54,20 @@ __global__ void geglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__
 
 // ---------------------------------------------------------------- AdamW
 // One kernel over the flat fp32 param/grad/m/v arenas (FusedAdamW).
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+// CLIP: the clip coefficient is rec[2] of the device record that
+// sumsq_finalize_kernel (grad_tail.hip) wrote. When it is not 1 the kernel
+// forms the clipped gradient as `flat_grad.mul_(coef)` would, stores it back
+// into the arena and updates from it; when it is 1 the arena is only read.
+// The branch is uniform over the grid. CLIP=false never touches rec or
+// writes g: it is the host-scalar kernel of step(), bit for bit.
+template <bool CLIP>
+__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v,
                              long n, float lr, float beta1, float beta2,
-                             float eps, float wd, float inv_bc1, float inv_bc2) {
+                             float eps, float wd, float inv_bc1, float inv_bc2,
+                             const float* __restrict__ rec) {
+  const float coef = CLIP ? rec[2] : 1.f;
+  const bool clip = CLIP && coef != 1.f;
   const long nvec = n / 4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
        i += (long)gridDim.x * blockDim.x) {
@@ -66,6 +76,10 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     f32x4 gv = load4<float>(g + e);
     f32x4 mv = load4<float>(m + e);
     f32x4 vv = load4<float>(v + e);
+    if (clip) {
+      gv.x *= coef; gv.y *= coef; gv.z *= coef; gv.w *= coef;
+      store4<float>(g + e, gv);
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float gg = (&gv.x)[k];
@@ -85,6 +99,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   long tail = nvec * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (tail < n) {
     float gg = g[tail];
+    if (clip) { gg *= coef; g[tail] = gg; }
     float mm = beta1 * m[tail] + (1.f - beta1) * gg;
     float vvk = beta2 * v[tail] + (1.f - beta2) * gg * gg;
     m[tail] = mm; v[tail] = vvk;
@@ -97,18 +112,32 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // reads bf16 grads, updates fp32 master + Adam state, writes bf16 params.
 // Removes the autocast weight-cast traffic (profiles/r01: ~10 ms/step of
 // bf16<->f32 copies) and halves DDP gradient bytes over xGMI.
+// CLIP as in adamw_kernel; here the coefficient is rounded to bf16 first,
+// the product is taken in fp32 and rounded to bf16 (what aten's bf16 mul_
+// by a 0-dim bf16 tensor computes), stored back, and widened again.
+template <bool CLIP>
 __global__ void adamw_bf16_kernel(__hip_bfloat16* __restrict__ p,
-                                  const __hip_bfloat16* __restrict__ g,
+                                  __hip_bfloat16* __restrict__ g,
                                   float* __restrict__ master,
                                   float* __restrict__ m, float* __restrict__ v,
                                   long n, float lr, float beta1, float beta2,
                                   float eps, float wd, float inv_bc1,
-                                  float inv_bc2) {
+                                  float inv_bc2, const float* __restrict__ rec) {
+  const float coef = CLIP ? rec[2] : 1.f;
+  const bool clip = CLIP && coef != 1.f;
+  const float cb = to_f32<__hip_bfloat16>(from_f32<__hip_bfloat16>(coef));
   const long nvec = n / 4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
        i += (long)gridDim.x * blockDim.x) {
     long e = i * 4;
     f32x4 gv = load4<__hip_bfloat16>(g + e);
+    if (clip) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        (&gv.x)[kk] = to_f32<__hip_bfloat16>(
+            from_f32<__hip_bfloat16>((&gv.x)[kk] * cb));
+      store4<__hip_bfloat16>(g + e, gv);
+    }
     f32x4 pv = load4<float>(master + e);
     f32x4 mv = load4<float>(m + e);
     f32x4 vv = load4<float>(v + e);
@@ -130,6 +159,11 @@ __global__ void adamw_bf16_kernel(__hip_bfloat16* __restrict__ p,
   long tail = nvec * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (tail < n) {
     float gg = to_f32<__hip_bfloat16>(g[tail]);
+    if (clip) {
+      __hip_bfloat16 gb = from_f32<__hip_bfloat16>(gg * cb);
+      g[tail] = gb;
+      gg = to_f32<__hip_bfloat16>(gb);
+    }
     float mm = beta1 * m[tail] + (1.f - beta1) * gg;
     float vvk = beta2 * v[tail] + (1.f - beta2) * gg * gg;
     m[tail] = mm; v[tail] = vvk;
@@ -409,8 +443,20 @@ void adamw_launch(float* p, const float* g, float* m, float* v, long n,
   float bc1 = 1.f - powf(b1, (float)step);
   float bc2 = 1.f - powf(b2, (float)step);
   dim3 grid(ew_blocks(n / 4)), block(256);
-  hipLaunchKernelGGL(adamw_kernel, grid, block, 0, s, p, g, m, v, n, lr, b1, b2,
-                     eps, wd, 1.f / bc1, 1.f / bc2);
+  hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, p,
+                     const_cast<float*>(g), m, v, n, lr, b1, b2, eps, wd,
+                     1.f / bc1, 1.f / bc2, (const float*)nullptr);
+}
+
+// clip-aware: rec = {sumsq, norm, coef} on the device; may rewrite g
+void adamw_clip_launch(float* p, float* g, float* m, float* v, long n,
+                       float lr, float b1, float b2, float eps, float wd,
+                       long step, const float* rec, hipStream_t s) {
+  float bc1 = 1.f - powf(b1, (float)step);
+  float bc2 = 1.f - powf(b2, (float)step);
+  dim3 grid(ew_blocks(n / 4)), block(256);
+  hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, p, g, m, v, n, lr,
+                     b1, b2, eps, wd, 1.f / bc1, 1.f / bc2, rec);
 }
 
 void adamw_bf16_launch(void* p, const void* g, float* master, float* m,
@@ -419,9 +465,22 @@ void adamw_bf16_launch(void* p, const void* g, float* master, float* m,
   float bc1 = 1.f - powf(b1, (float)step);
   float bc2 = 1.f - powf(b2, (float)step);
   dim3 grid(ew_blocks(n / 4)), block(256);
-  hipLaunchKernelGGL(adamw_bf16_kernel, grid, block, 0, s,
-                     (__hip_bfloat16*)p, (const __hip_bfloat16*)g, master, m, v,
-                     n, lr, b1, b2, eps, wd, 1.f / bc1, 1.f / bc2);
+  hipLaunchKernelGGL(adamw_bf16_kernel<false>, grid, block, 0, s,
+                     (__hip_bfloat16*)p, (__hip_bfloat16*)const_cast<void*>(g),
+                     master, m, v, n, lr, b1, b2, eps, wd, 1.f / bc1,
+                     1.f / bc2, (const float*)nullptr);
+}
+
+void adamw_bf16_clip_launch(void* p, void* g, float* master, float* m,
+                            float* v, long n, float lr, float b1, float b2,
+                            float eps, float wd, long step, const float* rec,
+                            hipStream_t s) {
+  float bc1 = 1.f - powf(b1, (float)step);
+  float bc2 = 1.f - powf(b2, (float)step);
+  dim3 grid(ew_blocks(n / 4)), block(256);
+  hipLaunchKernelGGL(adamw_bf16_kernel<true>, grid, block, 0, s,
+                     (__hip_bfloat16*)p, (__hip_bfloat16*)g, master, m, v, n,
+                     lr, b1, b2, eps, wd, 1.f / bc1, 1.f / bc2, rec);
 }
 
 // device-state AdamW (round-2 draft): norm -> prologue -> update on one

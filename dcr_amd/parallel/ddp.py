@@ -93,7 +93,9 @@ class GradBucketAllReduce:
         # batched copy of this bucket's autograd grads into the arena
         # slice, then SUM all-reduce + post-scale (bf16 grads: pre-divide
         # would lose mantissa)
-        self.opt.gather_grads(b.params)
+        # no fused sum of squares here: the all-reduce changes the values
+        self.opt.gather_grads(b.params, sumsq=False)
+        self.opt.arena_written()
         sl = self.opt.flat_grad[b.start:b.end]
         b.work = dist.all_reduce(sl, group=self.pg, async_op=True)
 
@@ -122,6 +124,7 @@ class GradBucketAllReduce:
             if b.work is not None:
                 b.work.wait()
         if launched and self.world > 1:
+            self.opt.arena_written()
             self.opt.flat_grad.div_(self.world)
         self._reset()
 

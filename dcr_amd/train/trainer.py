@@ -375,6 +375,7 @@ class Trainer:
                     # grads were all-reduced BEFORE unscaling, so an overflow
                     # on any rank propagates to every rank -> consistent skip
                     inv = 1.0 / self.scaler.get_scale()
+                    self.optimizer.arena_written()
                     self.optimizer.flat_grad.mul_(inv)
                     grads_finite = bool(
                         torch.isfinite(self.optimizer.flat_grad).all())
@@ -384,8 +385,8 @@ class Trainer:
                         # device-state path: clip fused into the kernels
                         self.optimizer.step_dev(lr=lr_step)
                     else:
-                        self.optimizer.clip_grad_norm_(cfg.max_grad_norm)
-                        self.optimizer.step(lr=lr_step)
+                        self.optimizer.clip_and_step(cfg.max_grad_norm,
+                                                     lr=lr_step)
                     if self.scaler is not None:
                         # growth bookkeeping is done manually (we never call
                         # scaler.step()/unscale_(), so a bare update() would
