@@ -9,18 +9,19 @@ this optimizer re-parameterizes the model so that
 * gradients land in one contiguous flat arena via ``gather_grads()``
   (autograd owns per-param grads; no per-param adds): on the GPU one
   ``grad_gather_kernel`` launch copies the whole list and takes its sum of
-  squares on the way (ops/hip/grad_tail.hip); accumulation micro-steps and
-  gradients whose layout differs from their arena view go through batched
-  ``_foreach`` kernels / ``copy_``,
+  squares on the way, and accumulation micro-steps add through the same
+  kernel's add mode (ops/hip/grad_tail.hip); gradients whose layout differs
+  from their arena view go through ``copy_`` / ``add_``,
 * Adam state (m, v) are two more flat buffers,
 
 so one step is ONE elementwise HIP kernel over four flat arrays —
 HBM-bound by design (~8 TB/s on MI355X), and the flat grad buffer doubles
 as the bucket arena for RCCL all-reduce (dcr_amd/parallel/ddp.py).
 ``clip_and_step()`` is the training step's tail: the global-norm clip
-coefficient stays on the device and the AdamW kernel applies it, so the
-host never waits for the norm. ``DCR_FUSED_GRAD_TAIL=0`` (read per call)
-restores the ``_foreach_copy_`` / ``vector_norm`` / host-compare path.
+coefficient stays on the device and the AdamW kernel (fp32 or FP8 state)
+applies it, so the host never waits for the norm. ``DCR_FUSED_GRAD_TAIL=0``
+(read per call) restores the ``_foreach_copy_`` / ``_foreach_add_`` /
+``vector_norm`` / host-compare path.
 
 Flatten AFTER moving the model to its device; ``p.data`` is replaced by
 buffer views.
@@ -273,9 +274,11 @@ class FusedAdamW:
         """Declare that ``flat_grad`` holds, or is about to hold, values the
         fused sum of squares did not see. EVERY site that writes the arena
         outside ``grad_gather_kernel``'s own full-coverage copy calls this:
-        add-mode and partial gathers, the per-parameter fallback copy,
-        ``_ensure_cold_slices``' zeroing, ``zero_grad``, the clip's ``mul_``
-        and the clipped store-back of the AdamW kernel, and outside this
+        add-mode gathers (the kernel's add mode takes no sum, and
+        ``_foreach_add_`` has none), partial gathers, the per-parameter
+        fallback copy / add, ``_ensure_cold_slices``' zeroing, ``zero_grad``,
+        the clip's ``mul_`` and the clipped store-back of the AdamW kernels
+        (fp32 and FP8 state), and outside this
         class the bucket all-reduce and ``div_`` of
         ``GradBucketAllReduce`` and the fp16 scaler's ``mul_`` in
         ``Trainer.train_step``. A new writer of the arena must call it too:
@@ -313,9 +316,14 @@ class FusedAdamW:
         gradient whose dtype or memory layout differs from its arena view
         is copied with ``copy_``. When one call copies EVERY parameter that
         way and ``sumsq`` is on, the kernel also leaves the arena's sum of
-        squares in ``_partials`` and the validity flag is set. Adds use
-        ``_foreach_add_``; without the native path (CPU, switch off, stream
-        capture) the copies use ``_foreach_copy_``."""
+        squares in ``_partials`` and the validity flag is set. The adds are
+        one launch of the same kernel in add mode (``dst = T(float(dst) +
+        float(src))``, the rounded add of ``_foreach_add_``), with ``add_``
+        for a gradient the kernel does not take; an add never leaves a valid
+        sum, so the step after accumulation takes the standalone pass. A call
+        that copies some parameters and adds to others issues both launches.
+        Without the native path (CPU, switch off, stream capture) the copies
+        use ``_foreach_copy_`` and the adds ``_foreach_add_``."""
         m = self._native_tail()
         copy_d, copy_s, add_d, add_s = [], [], [], []
         for p in (params if params is not None else self.params):
@@ -351,7 +359,14 @@ class FusedAdamW:
             if self.flat_grad.is_cuda:
                 count_dispatch('grad_gather_foreach')
             torch._foreach_copy_(copy_d, copy_s)
-        if add_d:
+        if add_d and m is not None:
+            rejected = m.grad_gather(self.flat_grad, add_d, add_s, None,
+                                     GATHER_CH, GATHER_GRID, True)
+            count_dispatch('grad_gather_add')
+            for i in rejected:
+                count_dispatch('grad_gather_fallback')
+                add_d[i].add_(add_s[i])
+        elif add_d:
             torch._foreach_add_(add_d, add_s)
 
     @torch.no_grad()
@@ -519,14 +534,15 @@ class FusedAdamW:
         the clipped gradient back into the arena when it is not 1, so the
         arena, parameters, master copy and moments end as the two calls
         leave them. Returns the gradient norm as a 0-dim device tensor (a
-        view of the record: the next call overwrites it). CPU, 8-bit state,
+        view of the record: the next call overwrites it). 8-bit state runs
+        the same tail with ``adamw8_kernel<P, true>``. CPU,
         ``DCR_FUSED_GRAD_TAIL=0`` and stream capture take the two calls.
 
         ``max_norm`` means what it means to ``clip_grad_norm_``, on every
         path: the gradient is scaled whenever ``norm > max_norm``, so
         ``max_norm = 0`` does NOT switch clipping off, it zeroes the
         gradient, and a negative ``max_norm`` flips its sign."""
-        m = self._native_tail() if self.state_bits == 32 else None
+        m = self._native_tail()
         if m is None:
             norm = self.clip_grad_norm_(max_norm)
             self.step(lr=lr)
@@ -537,6 +553,19 @@ class FusedAdamW:
         if lr is not None:
             self.lr = lr
         self.step_count += 1
+        if self.state_bits == 8:
+            count_dispatch('adamw8')
+            count_dispatch('adamw8_clip')
+            state = (self.exp_avg_q, self.exp_avg_absmax, self.exp_avg_sq_q,
+                     self.exp_avg_sq_absmax, self.lr, self.beta1, self.beta2,
+                     self.eps, self.weight_decay, self.step_count, rec)
+            if self.master is not None:
+                m.adamw8_step_bf16_clip(self.flat_param, self.flat_grad,
+                                        self.master, *state)
+            else:
+                m.adamw8_step_clip(self.flat_param, self.flat_grad, *state)
+            self.arena_written()  # the kernel stores the clipped gradient back
+            return rec[1]
         count_dispatch('adamw')
         count_dispatch('adamw_clip')
         if self.master is not None:

@@ -83,14 +83,29 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 
 // P = float (params updated in place) or __hip_bfloat16 (bf16 params out,
 // fp32 master in/out).
-template <typename P>
+// CLIP follows adamw_kernel<CLIP> (elementwise.hip): the clip coefficient is
+// rec[2] of the device record that sumsq_finalize_kernel (grad_tail.hip)
+// wrote. When it is not 1 the kernel forms the clipped gradient as
+// `flat_grad.mul_(coef.to(dtype))` would (fp32: g * coef; bf16: coef rounded
+// to bf16, product in fp32, rounded to bf16, widened again), stores it back
+// into the arena and updates from it; when it is 1 the arena is only read.
+// The branch is uniform over the grid. CLIP=false never touches rec or
+// writes g (g is const there): it is the kernel of step(), bit for bit.
+template <typename P, bool CLIP>
 __global__ __launch_bounds__(256) void adamw8_kernel(
-    P* __restrict__ p, const P* __restrict__ g, float* __restrict__ master,
+    P* __restrict__ p,
+    typename std::conditional<CLIP, P, const P>::type* __restrict__ g,
+    float* __restrict__ master,
     uint8_t* __restrict__ mq, float* __restrict__ mabs,
     uint8_t* __restrict__ rq, float* __restrict__ rabs, long n, long nblocks,
     float lr, float beta1, float omb1, float beta2, float omb2, float eps,
-    float wd, float inv_bc1, float inv_bc2) {
+    float wd, float inv_bc1, float inv_bc2, const float* __restrict__ rec) {
   constexpr bool BF16 = !std::is_same<P, float>::value;
+  float coef = 1.f;
+  if constexpr (CLIP) coef = rec[2];
+  const bool clip = CLIP && coef != 1.f;
+  // what aten's mul_ by a 0-dim tensor of the arena's dtype multiplies by
+  const float cm = BF16 ? to_f32<P>(from_f32<P>(coef)) : coef;
   const int lane = threadIdx.x % DCR_WAVE;
   // fp32 params: the "master" IS the param arena
   float* __restrict__ w32 = BF16 ? master : reinterpret_cast<float*>(p);
@@ -117,6 +132,22 @@ __global__ __launch_bounds__(256) void adamw8_kernel(
         const bool ok = e0 + k < n;
         gv[k] = ok ? to_f32<P>(g[e0 + k]) : 0.f;
         pv[k] = ok ? w32[e0 + k] : 0.f;
+      }
+    }
+    if constexpr (CLIP) {
+      if (clip) {
+        // masked elements stay 0 and are not stored
+#pragma unroll
+        for (int k = 0; k < EPL; ++k)
+          if (full || e0 + k < n) gv[k] = to_f32<P>(from_f32<P>(gv[k] * cm));
+        if (full) {
+          f32x4 t = {gv[0], gv[1], gv[2], gv[3]};
+          store4<P>(g + e0, t);
+        } else {
+#pragma unroll
+          for (int k = 0; k < EPL; ++k)
+            if (e0 + k < n) g[e0 + k] = from_f32<P>(gv[k]);
+        }
       }
     }
     // codes are allocated to nblocks*256, padding included
@@ -165,17 +196,44 @@ __global__ __launch_bounds__(256) void adamw8_kernel(
   }
 }
 
-template <typename P>
-void launch(void* p, const void* g, float* master, uint8_t* mq, float* mabs,
-            uint8_t* rq, float* rabs, long n, float lr, float b1, float omb1,
-            float b2, float omb2, float eps, float wd, float ibc1, float ibc2,
+// CLIP=false: the kernel of step(), g only read (rec unused, null);
+// CLIP=true: the clip-aware kernel, which may write g
+template <typename P, bool CLIP>
+void launch(void* p, typename std::conditional<CLIP, void, const void>::type* g,
+            float* master, uint8_t* mq, float* mabs, uint8_t* rq, float* rabs,
+            long n, float lr, float b1, float omb1, float b2, float omb2,
+            float eps, float wd, float ibc1, float ibc2, const float* rec,
             hipStream_t s) {
+  using G = typename std::conditional<CLIP, P, const P>::type;
   const long nblocks = (n + QBLOCK - 1) / QBLOCK;
   long wgs = (nblocks + BPWG - 1) / BPWG;
   if (wgs > MAX_WGS) wgs = MAX_WGS;   // grid-stride covers the rest
-  hipLaunchKernelGGL((adamw8_kernel<P>), dim3((unsigned)wgs), dim3(256), 0, s,
-                     (P*)p, (const P*)g, master, mq, mabs, rq, rabs, n,
-                     nblocks, lr, b1, omb1, b2, omb2, eps, wd, ibc1, ibc2);
+  hipLaunchKernelGGL((adamw8_kernel<P, CLIP>), dim3((unsigned)wgs), dim3(256),
+                     0, s, (P*)p, (G*)g, master, mq, mabs, rq, rabs, n, nblocks,
+                     lr, b1, omb1, b2, omb2, eps, wd, ibc1, ibc2, rec);
+}
+
+template <bool CLIP>
+void launch_dtype(int bf16, void* p,
+                  typename std::conditional<CLIP, void, const void>::type* g,
+                  float* master, uint8_t* mq, float* mabs, uint8_t* rq,
+                  float* rabs, long n, double lr, double b1, double b2,
+                  double eps, double wd, long step, const float* rec,
+                  hipStream_t s) {
+  if (n <= 0) return;
+  // scalars are formed in double and rounded once, exactly as the CPU
+  // reference does (python floats -> fp32 tensor scalars)
+  const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2);
+  const float ibc1 = (float)(1.0 / (1.0 - std::pow(b1, (double)step)));
+  const float ibc2 = (float)(1.0 / (1.0 - std::pow(b2, (double)step)));
+  if (bf16)
+    launch<__hip_bfloat16, CLIP>(p, g, master, mq, mabs, rq, rabs, n, (float)lr,
+                                 (float)b1, omb1, (float)b2, omb2, (float)eps,
+                                 (float)wd, ibc1, ibc2, rec, s);
+  else
+    launch<float, CLIP>(p, g, master, mq, mabs, rq, rabs, n, (float)lr,
+                        (float)b1, omb1, (float)b2, omb2, (float)eps, (float)wd,
+                        ibc1, ibc2, rec, s);
 }
 
 }  // namespace
@@ -186,19 +244,17 @@ void adamw8_launch(int bf16, void* p, const void* g, float* master,
                    unsigned char* mq, float* mabs, unsigned char* rq,
                    float* rabs, long n, double lr, double b1, double b2,
                    double eps, double wd, long step, hipStream_t s) {
-  if (n <= 0) return;
-  // scalars are formed in double and rounded once, exactly as the CPU
-  // reference does (python floats -> fp32 tensor scalars)
-  const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2);
-  const float ibc1 = (float)(1.0 / (1.0 - std::pow(b1, (double)step)));
-  const float ibc2 = (float)(1.0 / (1.0 - std::pow(b2, (double)step)));
-  if (bf16)
-    launch<__hip_bfloat16>(p, g, master, mq, mabs, rq, rabs, n, (float)lr,
-                           (float)b1, omb1, (float)b2, omb2, (float)eps,
-                           (float)wd, ibc1, ibc2, s);
-  else
-    launch<float>(p, g, master, mq, mabs, rq, rabs, n, (float)lr, (float)b1,
-                  omb1, (float)b2, omb2, (float)eps, (float)wd, ibc1, ibc2, s);
+  launch_dtype<false>(bf16, p, g, master, mq, mabs, rq, rabs, n, lr, b1, b2,
+                      eps, wd, step, nullptr, s);
+}
+
+void adamw8_clip_launch(int bf16, void* p, void* g, float* master,
+                        unsigned char* mq, float* mabs, unsigned char* rq,
+                        float* rabs, long n, double lr, double b1, double b2,
+                        double eps, double wd, long step, const float* rec,
+                        hipStream_t s) {
+  launch_dtype<true>(bf16, p, g, master, mq, mabs, rq, rabs, n, lr, b1, b2, eps,
+                     wd, step, rec, s);
 }
 
 }  // namespace dcr

@@ -373,12 +373,17 @@ float* gt_partials(const c10::optional<at::Tensor>& partials,
 // Copies every qualifying grads[i] into views[i] (views of `arena`) in one
 // launch; with `partials` also writes each virtual block's sum of squares.
 // Returns the indices that did not qualify: the caller copies those.
+// add: views[i] += grads[i] (one fp32 add rounded once, as _foreach_add_)
+// instead of the copy, same eligibility rule; takes no partials. The caller
+// runs view.add_(g) for the indices returned.
 std::vector<int64_t> grad_gather(at::Tensor arena, std::vector<at::Tensor> views,
                                  std::vector<at::Tensor> grads,
                                  c10::optional<at::Tensor> partials,
-                                 int64_t ch, int64_t grid) {
+                                 int64_t ch, int64_t grid, bool add) {
   gt_check_arena(arena, ch);
   TORCH_CHECK(views.size() == grads.size(), "grad_gather: list lengths differ");
+  TORCH_CHECK(!add || !partials.has_value(),
+              "grad_gather: add mode takes no sum of squares");
   std::vector<int64_t> rows, rejected;
   rows.reserve(4 * views.size());
   int64_t nvb = 0;
@@ -401,7 +406,7 @@ std::vector<int64_t> grad_gather(at::Tensor arena, std::vector<at::Tensor> views
   auto table = gt_upload(arena, rows);
   grad_gather_launch(dtype_of(arena), (const long*)table.data_ptr<int64_t>(),
                      (int)(rows.size() / 4), nvb, arena.data_ptr(), pp, (int)ch,
-                     grad_gather_grid(nvb, (int)grid), /*store=*/true,
+                     grad_gather_grid(nvb, (int)grid), /*store=*/true, add,
                      cur_stream());
   return rejected;
 }
@@ -432,7 +437,7 @@ int64_t grad_sumsq(at::Tensor arena, std::vector<at::Tensor> views,
   grad_gather_launch(dtype_of(arena), (const long*)table.data_ptr<int64_t>(),
                      (int)(rows.size() / 4), nvb, arena.data_ptr(), pp, (int)ch,
                      grad_gather_grid(nvb, (int)grid), /*store=*/false,
-                     cur_stream());
+                     /*add=*/false, cur_stream());
   return nvb;
 }
 
@@ -569,6 +574,51 @@ void adamw8_step_bf16(at::Tensor p, at::Tensor g, at::Tensor master,
                 mq.data_ptr<uint8_t>(), mabs.data_ptr<float>(),
                 rq.data_ptr<uint8_t>(), rabs.data_ptr<float>(), p.numel(), lr,
                 beta1, beta2, eps, wd, step, cur_stream());
+}
+
+// clip-aware: rec = {sumsq, norm, coef} from sumsq_finalize; when coef != 1
+// the clipped gradient is stored back into g
+void adamw8_step_clip(at::Tensor p, at::Tensor g, at::Tensor mq,
+                      at::Tensor mabs, at::Tensor rq, at::Tensor rabs,
+                      double lr, double beta1, double beta2, double eps,
+                      double wd, int64_t step, at::Tensor rec) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat,
+              "adamw8_clip: fp32 flat params expected");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kFloat &&
+              g.numel() == p.numel(), "adamw8_clip: fp32 grads of the same numel");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous(),
+              "adamw8_clip: arenas must be contiguous");
+  adamw8_check_state(p, mq, mabs, rq, rabs);
+  gt_check_rec(rec, p);
+  adamw8_clip_launch(0, p.data_ptr(), g.data_ptr(), nullptr,
+                     mq.data_ptr<uint8_t>(), mabs.data_ptr<float>(),
+                     rq.data_ptr<uint8_t>(), rabs.data_ptr<float>(), p.numel(),
+                     lr, beta1, beta2, eps, wd, step, rec.data_ptr<float>(),
+                     cur_stream());
+}
+
+void adamw8_step_bf16_clip(at::Tensor p, at::Tensor g, at::Tensor master,
+                           at::Tensor mq, at::Tensor mabs, at::Tensor rq,
+                           at::Tensor rabs, double lr, double beta1,
+                           double beta2, double eps, double wd, int64_t step,
+                           at::Tensor rec) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kBFloat16,
+              "adamw8_bf16_clip: bf16 flat params expected");
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == at::kBFloat16 &&
+              g.numel() == p.numel(),
+              "adamw8_bf16_clip: bf16 grads of the same numel");
+  TORCH_CHECK(master.is_cuda() && master.scalar_type() == at::kFloat &&
+              master.numel() == p.numel(),
+              "adamw8_bf16_clip: fp32 master of the same numel");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && master.is_contiguous(),
+              "adamw8_bf16_clip: arenas must be contiguous");
+  adamw8_check_state(p, mq, mabs, rq, rabs);
+  gt_check_rec(rec, p);
+  adamw8_clip_launch(1, p.data_ptr(), g.data_ptr(), master.data_ptr<float>(),
+                     mq.data_ptr<uint8_t>(), mabs.data_ptr<float>(),
+                     rq.data_ptr<uint8_t>(), rabs.data_ptr<float>(), p.numel(),
+                     lr, beta1, beta2, eps, wd, step, rec.data_ptr<float>(),
+                     cur_stream());
 }
 
 // ------------------------------------------------------------- scheduler math
@@ -1268,7 +1318,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adamw_step_bf16_clip", &adamw_step_bf16_clip);
   mod.def("grad_gather", &grad_gather, py::arg("arena"), py::arg("views"),
           py::arg("grads"), py::arg("partials") = py::none(),
-          py::arg("ch") = 16384, py::arg("grid") = 0);
+          py::arg("ch") = 16384, py::arg("grid") = 0, py::arg("add") = false);
   mod.def("grad_sumsq", &grad_sumsq, py::arg("arena"), py::arg("views"),
           py::arg("partials"), py::arg("ch") = 16384, py::arg("grid") = 0);
   mod.def("sumsq_finalize", &sumsq_finalize);
@@ -1282,6 +1332,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_absmax"), py::arg("lr"),
           py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
           py::arg("step"));
+  mod.def("adamw8_step_clip", &adamw8_step_clip, py::arg("p"), py::arg("g"),
+          py::arg("exp_avg_q"), py::arg("exp_avg_absmax"),
+          py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_absmax"), py::arg("lr"),
+          py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("wd"),
+          py::arg("step"), py::arg("rec"));
+  mod.def("adamw8_step_bf16_clip", &adamw8_step_bf16_clip, py::arg("p"),
+          py::arg("g"), py::arg("master"), py::arg("exp_avg_q"),
+          py::arg("exp_avg_absmax"), py::arg("exp_avg_sq_q"),
+          py::arg("exp_avg_sq_absmax"), py::arg("lr"), py::arg("beta1"),
+          py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("step"),
+          py::arg("rec"));
   mod.def("add_noise", &add_noise);
   mod.def("get_velocity", &get_velocity);
   mod.def("cfg_combine", &cfg_combine);

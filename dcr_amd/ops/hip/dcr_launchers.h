@@ -84,10 +84,12 @@ void adamw_bf16_clip_launch(void* p, void* g, float* master, float* m,
 // of one parameter (ch % 8 == 0), nvb their total. store: copy source to
 // arena; partials (nvb floats, uninitialised; may be null when store) gets
 // each virtual block's sum of squares. !store needs partials and only reads.
+// add (with store, partials ignored): arena = T(float(arena) + float(source))
+// instead of the copy; no sum of squares.
 int grad_gather_grid(long nvb, int grid_req);
 void grad_gather_launch(DType dt, const long* table, int nparams, long nvb,
                         void* arena, float* partials, int ch, int grid,
-                        bool store, hipStream_t s);
+                        bool store, bool add, hipStream_t s);
 void sumsq_finalize_launch(const float* partials, long nvb, float max_norm,
                            float* rec, hipStream_t s);
 // device-state AdamW (round-2 draft; hipGraph-capturable step)
@@ -101,6 +103,12 @@ void adamw8_launch(int bf16, void* p, const void* g, float* master,
                    unsigned char* mq, float* mabs, unsigned char* rq,
                    float* rabs, long n, double lr, double b1, double b2,
                    double eps, double wd, long step, hipStream_t s);
+// clip-aware: rec as for adamw_clip_launch; may rewrite g
+void adamw8_clip_launch(int bf16, void* p, void* g, float* master,
+                        unsigned char* mq, float* mabs, unsigned char* rq,
+                        float* rabs, long n, double lr, double b1, double b2,
+                        double eps, double wd, long step, const float* rec,
+                        hipStream_t s);
 void sched_launch(DType dt, int mode, const void* x0, const void* noise,
                   const float* ac, const long* t, void* out, long per_sample,
                   long total, hipStream_t s);

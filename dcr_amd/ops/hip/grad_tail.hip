@@ -20,6 +20,13 @@
 // with the widest access of 16 / 8 / 4 / 2 bytes that divides the distance
 // between source and destination; the destination group is always stored
 // as one 16-byte access.
+//
+// ADD (gradient accumulation micro-steps): dst = T(float(dst) + float(src)),
+// one fp32 add rounded once, which is what `_foreach_add_` computes for bf16
+// and fp32. Same element-to-lane map and source widths; the destination
+// group is one 16-byte load and one 16-byte store, GT_UNROLL loads of both
+// operands in flight. There is no fused sum of squares in add mode: the sum
+// of a step's gradient is taken by the standalone pass.
 
 #include <cstdint>
 
@@ -80,8 +87,38 @@ __device__ __forceinline__ float gt_group_sumsq<__hip_bfloat16>(uint4 v) {
   return (q[0] + q[1]) + (q[2] + q[3]);
 }
 
+// a + b over one 16-byte group, each element one fp32 add rounded to T
+template <typename T>
+__device__ __forceinline__ uint4 gt_group_add(uint4 a, uint4 b);
+
+template <>
+__device__ __forceinline__ uint4 gt_group_add<float>(uint4 a, uint4 b) {
+  return make_uint4(__float_as_uint(__uint_as_float(a.x) + __uint_as_float(b.x)),
+                    __float_as_uint(__uint_as_float(a.y) + __uint_as_float(b.y)),
+                    __float_as_uint(__uint_as_float(a.z) + __uint_as_float(b.z)),
+                    __float_as_uint(__uint_as_float(a.w) + __uint_as_float(b.w)));
+}
+
+__device__ __forceinline__ unsigned gt_bf16_bits(float f) {
+  __hip_bfloat16 h = from_f32<__hip_bfloat16>(f);
+  return (unsigned)*reinterpret_cast<unsigned short*>(&h);
+}
+
+template <>
+__device__ __forceinline__ uint4 gt_group_add<__hip_bfloat16>(uint4 a, uint4 b) {
+  uint4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    unsigned x = (&a.x)[k], y = (&b.x)[k];
+    float lo = __uint_as_float(x << 16) + __uint_as_float(y << 16);
+    float hi = __uint_as_float(x & 0xffff0000u) + __uint_as_float(y & 0xffff0000u);
+    (&r.x)[k] = gt_bf16_bits(lo) | (gt_bf16_bits(hi) << 16);
+  }
+  return r;
+}
+
 // the 16-byte groups of one chunk; lane t takes groups t, t+256, ... in order
-template <typename T, int W, bool SUMSQ, bool STORE>
+template <typename T, int W, bool SUMSQ, bool STORE, bool ADD>
 __device__ __forceinline__ float gt_body(const T* __restrict__ src,
                                          T* __restrict__ dst, int ng, float s) {
 #pragma clang fp contract(off)
@@ -93,6 +130,14 @@ __device__ __forceinline__ float gt_body(const T* __restrict__ src,
     for (int u = 0; u < GT_UNROLL; ++u)
       v[u] = gt_load16<W>(reinterpret_cast<const char*>(
           src + (long)(g + u * GT_THREADS) * G));
+    if (ADD) {
+      uint4 d[GT_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GT_UNROLL; ++u)
+        d[u] = *reinterpret_cast<const uint4*>(dst + (long)(g + u * GT_THREADS) * G);
+#pragma unroll
+      for (int u = 0; u < GT_UNROLL; ++u) v[u] = gt_group_add<T>(d[u], v[u]);
+    }
     if (STORE) {
 #pragma unroll
       for (int u = 0; u < GT_UNROLL; ++u)
@@ -105,13 +150,15 @@ __device__ __forceinline__ float gt_body(const T* __restrict__ src,
   }
   for (; g < ng; g += GT_THREADS) {
     uint4 v = gt_load16<W>(reinterpret_cast<const char*>(src + (long)g * G));
+    if (ADD)
+      v = gt_group_add<T>(*reinterpret_cast<const uint4*>(dst + (long)g * G), v);
     if (STORE) *reinterpret_cast<uint4*>(dst + (long)g * G) = v;
     if (SUMSQ) s = s + gt_group_sumsq<T>(v);
   }
   return s;
 }
 
-template <typename T, bool SUMSQ, bool STORE>
+template <typename T, bool SUMSQ, bool STORE, bool ADD = false>
 __global__ __launch_bounds__(GT_THREADS)
 void grad_gather_kernel(const long* __restrict__ table, int nparams, long nvb,
                         T* __restrict__ arena, float* __restrict__ partials,
@@ -144,6 +191,7 @@ void grad_gather_kernel(const long* __restrict__ table, int nparams, long nvb,
     if (t < h) {
 #pragma clang fp contract(off)
       T x = src[t];
+      if (ADD) x = from_f32<T>(to_f32<T>(dst[t]) + to_f32<T>(x));
       if (STORE) dst[t] = x;
       float f = to_f32<T>(x);
       if (SUMSQ) s = f * f;
@@ -153,17 +201,18 @@ void grad_gather_kernel(const long* __restrict__ table, int nparams, long nvb,
     const T* bs = src + h;
     T* bd = dst + h;
     if ((d & 15u) == 0)
-      s = gt_body<T, 16, SUMSQ, STORE>(bs, bd, ng, s);
+      s = gt_body<T, 16, SUMSQ, STORE, ADD>(bs, bd, ng, s);
     else if ((d & 7u) == 0)
-      s = gt_body<T, 8, SUMSQ, STORE>(bs, bd, ng, s);
+      s = gt_body<T, 8, SUMSQ, STORE, ADD>(bs, bd, ng, s);
     else if ((d & 3u) == 0)
-      s = gt_body<T, 4, SUMSQ, STORE>(bs, bd, ng, s);
+      s = gt_body<T, 4, SUMSQ, STORE, ADD>(bs, bd, ng, s);
     else
-      s = gt_body<T, sizeof(T) < 4 ? 2 : 4, SUMSQ, STORE>(bs, bd, ng, s);
+      s = gt_body<T, sizeof(T) < 4 ? 2 : 4, SUMSQ, STORE, ADD>(bs, bd, ng, s);
     if (t < r) {
 #pragma clang fp contract(off)
       const int i = h + ng * G + t;
       T x = src[i];
+      if (ADD) x = from_f32<T>(to_f32<T>(dst[i]) + to_f32<T>(x));
       if (STORE) dst[i] = x;
       float f = to_f32<T>(x);
       if (SUMSQ) s = s + f * f;
@@ -228,10 +277,13 @@ int grad_gather_grid(long nvb, int grid_req) {
 template <typename T>
 static void gather_dispatch(const long* table, int nparams, long nvb, void* arena,
                             float* partials, int ch, int grid, bool store,
-                            hipStream_t s) {
+                            bool add, hipStream_t s) {
   dim3 gr(grid), bl(GT_THREADS);
   T* a = (T*)arena;
-  if (store && partials)
+  if (add)
+    hipLaunchKernelGGL((grad_gather_kernel<T, false, true, true>), gr, bl, 0, s,
+                       table, nparams, nvb, a, (float*)nullptr, ch);
+  else if (store && partials)
     hipLaunchKernelGGL((grad_gather_kernel<T, true, true>), gr, bl, 0, s, table,
                        nparams, nvb, a, partials, ch);
   else if (store)
@@ -244,14 +296,14 @@ static void gather_dispatch(const long* table, int nparams, long nvb, void* aren
 
 void grad_gather_launch(DType dt, const long* table, int nparams, long nvb,
                         void* arena, float* partials, int ch, int grid,
-                        bool store, hipStream_t s) {
+                        bool store, bool add, hipStream_t s) {
   if (nvb <= 0 || nparams <= 0) return;
   if (dt == DT_BF16)
     gather_dispatch<__hip_bfloat16>(table, nparams, nvb, arena, partials, ch,
-                                    grid, store, s);
+                                    grid, store, add, s);
   else
     gather_dispatch<float>(table, nparams, nvb, arena, partials, ch, grid,
-                           store, s);
+                           store, add, s);
 }
 
 void sumsq_finalize_launch(const float* partials, long nvb, float max_norm,

@@ -407,6 +407,12 @@ class Trainer:
                     self.scaler.update(self.scaler.get_scale() * 0.5)
                 self.optimizer.zero_grad()
             self.global_step += 1
+        else:
+            # hand the micro-step's gradient to the arena now (scaled, with
+            # the fp16 scaler: unscaled once on the sync step): with p.grad
+            # left set the next backward would accumulate through one add_
+            # per parameter and keep a second copy of the gradient alive
+            self.optimizer.gather_grads()
         return loss.detach()
 
     # ------------------------------------------------------------------
